@@ -15,10 +15,13 @@ rows exist only after the previous step's commit + the drafter and target forwar
 `--fused-prepare 0 --spec-rows 3` is the three-launch form (lantern_prepare_step = O6 + the 3 most likely rows of O7 as its own launch in front).  The round-5 variant that hid
 the prepare stage in the PREVIOUS step's commit launch is only possible on pre-generated pools: a harness-only extra of the three-launch form, never `value`.
 `--groups 1 --no-fuse-o7 --spec-rows 0` is the four-launch step (every row through cfg_mask_topk first).
-N > 1 prints BOTH scaling forms in the one line: `value` = weak scaling (--seqs-per-gpu on every rank) and `c5_strong` = BASELINE config C5 / BASELINE.md section 2
-(64 sequences in ALL, split evenly over the ranks: run.sh:76-91), each with its own barrier-bracketed K-step timed region.
+A plain run sets up, warms up, times exactly --steps steps and prints the line (`value`, `ms_per_step` = milliseconds per timed step, ...);
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (seeded inputs: identical from run to run).  Everything
+below is measured with --full only.  With --full, N > 1 prints BOTH scaling forms in the one line: `value` = weak scaling (--seqs-per-gpu on
+every rank) and `c5_strong` = BASELINE config C5 / BASELINE.md section 2 (64 sequences in ALL, split evenly over the ranks: run.sh:76-91),
+each with its own barrier-bracketed K-step timed region.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline      evaluate_posterior of the timed configuration: algorithmic bytes (SURVEY 8d contract formula, from the kernel's own
                 counters) / its mean launch duration (HIP events recorded by the launch itself); peak 8000 GB/s.  `windowed_kernel`: the bytes
                 the windowed design really has to move; `traffic`: PMC bytes from profiles/r06_ep_traffic.json (refused when measured on other kernel
@@ -125,7 +128,17 @@ def parse():
     ap.add_argument("--dist-backend", choices=["auto", "nccl", "gloo"], default="auto",
                     help="process group of the N > 1 run (used for the timing barrier and three scalars only: the accept path has no collective).  "
                          "auto = nccl (RCCL), falling back to gloo on host tensors when the RCCL group cannot be brought up -- decided before any kernel is launched")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the event-timed per-kernel pass (roofline, kernels), the extra runs (--no-extras), the "
+                         "evaluate_posterior sweep (--ep-sweep), the CPU baseline (--cpu-seconds) and, with N > 1, the C5 strong-scaling leg.  Without it a "
+                         "run sets up, warms up, times the --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step handed its caller (verdicts, bonus tokens, candidates, accepted tokens "
+                         "and hidden rows, KV lengths) as DIR/<name>.npy, float32 / float64, <= 64 MiB in all; N > 1: every rank, names prefixed rank<r>_")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 # ----------------------------------------------------------------------------- CPU baseline
@@ -1217,7 +1230,7 @@ def stub_rank(args, world, rank):
     dt_all, tokens_all = reduce_timing(dist if world > 1 else None, dt, float(K * per_step), group=pg["group"] if pg else None)
     ranks_seen = count_ranks(dist, pg)
     c5 = None
-    if world > 1 and args.total_seqs == 0:          # the second leg of an N > 1 run: 64 sequences in all (same control flow as main())
+    if args.full and world > 1 and args.total_seqs == 0:          # the second leg of an N > 1 run: 64 sequences in all (same control flow as main())
         plan = c5_strong_plan(world, cap_groups(args, world))
         if plan is None:
             c5 = {"skipped": f"{C5_TOTAL} sequences do not split evenly over {world} ranks"}
@@ -1235,16 +1248,53 @@ def stub_rank(args, world, rank):
         out = {"metric": "stub", "value": tokens_all / dt_all, "unit": "accepted_tokens/s", "n_gpus": world, "steps": K,
                "warmup": args.warmup, "ms_per_step": 1e3 * dt_all / K, "data": "stub", "tokens": tokens_all, "scaling": scaling,
                "sequences_per_rank": n_seq, "groups": _groups, "ranks_seen": ranks_seen, "backend": pg["backend"] if pg else None,
-               "backend_note": pg["note"] if pg else None, **({"c5_strong": c5} if c5 is not None else {}),
-               # a stand-in for the extras of a real run (tests/test_multiproc_cpu.py: they must stay off the stdout line)
-               "roofline": {"bound": "hbm", "achieved": 0.0, "peak": 8000.0, "unit": "GB/s", "frac": 0.0, "traffic": None},
-               "cpu_baseline": {"value": 0.0, "unit": "accepted_tokens/s", "cores": 1, "kind": "port", "sample": "stub"},
-               "ep_batch_sweep": [{"sequences_per_launch": b, "pad": "x" * 512} for b in (1, 8, 64, 256, 512, 4096)],
-               "configs": {"pad": ["y" * 256] * 40}}
+               "backend_note": pg["note"] if pg else None, **({"c5_strong": c5} if c5 is not None else {})}
+        if args.full:          # a stand-in for the extras of a real --full run (tests/test_multiproc_cpu.py: they must stay off the stdout line)
+            out.update({"roofline": {"bound": "hbm", "achieved": 0.0, "peak": 8000.0, "unit": "GB/s", "frac": 0.0, "traffic": None},
+                        "cpu_baseline": {"value": 0.0, "unit": "accepted_tokens/s", "cores": 1, "kind": "port", "sample": "stub"},
+                        "ep_batch_sweep": [{"sequences_per_launch": b, "pad": "x" * 512} for b in (1, 8, 64, 256, 512, 4096)],
+                        "configs": {"pad": ["y" * 256] * 40}})
         emit(out, args)
     if world > 1:
         dist.barrier(group=pg["group"])
         close_process_group(dist, pg)
+
+
+# ------------------------------------------------------------------------------------ --dump-outputs
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(wl, out_dir: str, prefix: str = "") -> dict:
+    """What the LAST timed step handed its caller, one .npy per array (integers as float64, exact; bf16 hidden rows as float32, exact):
+    the verdict (best path, accept length, evaluate_posterior counters), the bonus token, the step's candidates, and the commit's results --
+    accepted tokens and hidden rows (positions past accept_len + 1 are not written by the step: -1 / 0 here) and the KV lengths [B, 2] (cond,
+    uncond) the next step starts from.  The KV slabs' rows are left out: nothing in this synthetic workload writes them, they stay zero.
+    Above DUMP_BUDGET_BYTES in all, every array is cut to the same fraction by a fixed-seed sample of its flat indices (same shapes, same sample).
+    Returns {name: shape}."""
+    i = wl.step_idx - 1
+    B, D = wl.cfg.n_seq, wl.D
+    alen = wl.log_alen[i].long()
+    f64 = lambda t: t.detach().to(torch.float64).cpu().numpy()
+    arrays = {"best": f64(wl.log_best[i]), "accept_len": f64(wl.log_alen[i]), "bonus_token": f64(wl.log_token[i]),
+              "counters": f64(wl.log_cnt[i]), "candidates": f64(wl.cand)}
+    if wl.cfg.with_kv:          # (the commit launch writes them; without KV slabs nothing does)
+        live = torch.arange(D, device=alen.device)[None, :] <= alen[:, None]                                   # [B, D]
+        arrays["accepted_tokens"] = f64(torch.where(live, wl.acc_tokens, torch.full_like(wl.acc_tokens, -1)))
+        hid = wl.out_hidden.float()                                                                              # [B, 2, D, HIDDEN]
+        arrays["accepted_hidden"] = torch.where(live[:, None, :, None], hid, torch.zeros_like(hid)).cpu().numpy()
+    nxt = wl.lens[(i & 1) ^ 1].view(wl.G, 2, wl.Bg)                                                           # per group [cond..., uncond...]
+    arrays["kv_lengths"] = f64(nxt.permute(0, 2, 1).reshape(B, 2))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        rng = np.random.default_rng(0)
+        for name, a in arrays.items():
+            keep = a.size * DUMP_BUDGET_BYTES // total
+            arrays[name] = a.reshape(-1)[np.sort(rng.choice(a.size, keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 # ------------------------------------------------------------------------------------ main
@@ -1354,12 +1404,17 @@ def main():
         wl.step()
     barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(wl, args.dump_outputs, "" if world == 1 else f"rank{rank}_")
+    # ---- everything below that is not the headline runs with --full only
+    full = args.full
     # ---- per-kernel durations: the same loop continues eagerly with HIP events on the launch stream for the three
     # HBM-heavy kernels (recorded at kernel begin / end by the launch itself: lantern_profile_next_launch), kept out of the
     # timed region so that `value` carries no event overhead.  rocprofv3 of this command sees both passes.
     evs = None
     KT = min(K, 100)
-    if not args.no_events:
+    if full and not args.no_events:
         evs = make_events(names, KT, device)
         for i in range(KT):
             wl.step(evs[i], serial=True)     # groups one after the other on one stream: undisturbed kernel durations
@@ -1402,15 +1457,18 @@ def main():
             "mean_accept_length": float(alen.mean()),
             "per_step": {"levels": float(cnt[..., 0].mean()), "tried": float(cnt[..., 1].mean()), "rejected": float(cnt[..., 2].mean())},
         }
+        if dumped is not None:
+            print(f"bench.py: last timed step's outputs in {args.dump_outputs}: {dumped}", file=sys.stderr)
         if evs:
             out["roofline"], out["kernels"] = kernel_report(wl, evs, W + K, W + K + KT, KT)
         # the CPU leg replays the run from step 0 (warm-up included): keep the logs before the extra runs below overwrite them
-        gb = wl.log_best[:n_logged].cpu().numpy()
-        ga = wl.log_alen[:n_logged].cpu().numpy()
-        gt = wl.log_token[:n_logged].cpu().numpy()
+        if full and args.cpu_seconds > 0 and world == 1:
+            gb = wl.log_best[:n_logged].cpu().numpy()
+            ga = wl.log_alen[:n_logged].cpu().numpy()
+            gt = wl.log_token[:n_logged].cpu().numpy()
     # ---- N > 1: BASELINE's own scaling form (C5: 64 sequences in ALL) beside the weak-scaling headline, in the same line.  Every rank takes part
     # (its barriers are collective); the weak run's KV slabs are released first (64 sequences per GPU fill the device).
-    if world > 1 and args.total_seqs == 0 and not args.no_kv and os.environ.get("LANTERN_BENCH_NO_C5") != "1":
+    if full and world > 1 and args.total_seqs == 0 and not args.no_kv and os.environ.get("LANTERN_BENCH_NO_C5") != "1":
         torch.cuda.synchronize(device)          # (device-wide; NOT join(): cross-stream event waits behind a deep queue slow its drain)
         wl.release_kv()
         c5 = c5_strong_run(args, cfg, world, rank, device, dist, group, red_device)
@@ -1418,7 +1476,7 @@ def main():
             c5["ranks_seen"] = ranks_seen
             out["c5_strong"] = c5
     if rank == 0:
-        if not args.no_extras and wl.windowed and world == 1:
+        if full and not args.no_extras and wl.windowed and world == 1:
             # LANTERN++ mode of the same workload (run B of BASELINE.md: lantern_delta = 5 -> tau = 4 * p(x)): same pools, same kernels
             KL = 60
             torch.cuda.synchronize(device)          # (device-wide; NOT join(): cross-stream event waits behind a deep queue slow its drain)
@@ -1455,29 +1513,29 @@ def main():
                 out["merged_prepare_harness_only"] = {"ms_per_step": 1e3 * dm / KL, "value": wl.accepted_tokens(15, 15 + KL) / dm, "steps": KL,
                                                       "note": "prepare_next: not a form a decode loop can run; never the headline"}
                 wl.cfg.merge_prepare = False
-        if (args.ep_sweep or not args.no_extras) and world == 1:
+        if full and (args.ep_sweep or not args.no_extras) and world == 1:
             wl.release_kv()      # the extra runs build their own workloads: give the memory back first
-        if not args.no_extras and world == 1 and wl.windowed:
+        if full and not args.no_extras and world == 1 and wl.windowed:
             out["per_kernel_single_group"] = {k: per_kernel_run(device, cfg, min(K, 60), ep_kernel=k, n_seq=(args.seqs_per_gpu if n_seq + args.groups > args.seqs_per_gpu else n_seq)) for k in ("chain", "nodes")}
             out["step_latency_us"] = step_latency(device, cfg)
             out["other_groupings"] = {f"groups_{g}": side_run(device, cfg, max(min(K, 100), 60), n_groups=g, commit_window=0, n_seq=args.seqs_per_gpu - args.seqs_per_gpu % g)
                                       for g in (1, 2) if g != cfg.n_groups}
-        if not args.no_extras and world == 1 and wl.windowed:
+        if full and not args.no_extras and world == 1 and wl.windowed:
             out["dynamic_tree"] = dynamic_run(device, cfg, min(K, 100), n_seq, fuse_o7=True)
             out["dynamic_tree"]["all_rows_by_cfg_mask_topk"] = {k: v for k, v in dynamic_run(device, cfg, min(K, 100), n_seq, fuse_o7=False).items()
                                                                 if k in ("value", "ms_per_step", "kernel_ms")}
-        if not args.no_extras and world == 1 and wl.windowed:
+        if full and not args.no_extras and world == 1 and wl.windowed:
             out["configs"] = other_configs(device, cfg, min(K, 60), n_seq)
-        if not args.no_extras and world == 1 and wl.windowed:
+        if full and not args.no_extras and world == 1 and wl.windowed:
             out["drafter_layer"] = drafter_layer_run()
             out["drafter_cycle"] = drafter_cycle_run()
             out["mirror_generate"] = mirror_generate_run()
-        if args.ep_sweep and world == 1:
+        if full and args.ep_sweep and world == 1:
             out["ep_batch_sweep"] = ep_batch_sweep([int(x) for x in args.ep_sweep.split(",") if x], device, cfg)
             sat = saturating_report(out["ep_batch_sweep"])
             if sat and "roofline" in out:
                 out["roofline"]["saturating"] = sat
-        if args.cpu_seconds > 0 and world == 1:      # the CPU baseline is reported at N = 1 only
+        if full and args.cpu_seconds > 0 and world == 1:      # the CPU baseline is reported at N = 1 only
             n_cpu = args.cpu_seqs or cfg.n_seq
             gpu_stream = [[(int(gb[i, b]), int(ga[i, b]), int(gt[i, b])) for b in range(cfg.n_seq)] for i in range(n_logged)]
             out["cpu_baseline"] = cpu_baseline(wl, args.cpu_seconds, n_cpu, gpu_stream, python_budget_s=min(args.cpu_seconds, 8.0))

@@ -104,14 +104,14 @@ def test_prompt_slices_and_statistics_files(tmp_path):
 
 @pytest.mark.timeout(300)
 def test_bench_gpus_2_starts_its_own_ranks():
-    """`python bench.py --gpus 2` with no launcher: two rank processes, gloo rendezvous on 127.0.0.1, rank 0's line says
+    """`python bench.py --gpus 2 --full` with no launcher: two rank processes, gloo rendezvous on 127.0.0.1, rank 0's line says
     n_gpus 2 and carries the SUM of both ranks' tokens (LANTERN_BENCH_STUB=1: the kernels are replaced by a sleep -- there is
     no GPU here; the launch / reduction control flow is what is under test).  A WORLD_SIZE that disagrees with --gpus fails."""
     import subprocess
     env = dict(os.environ, LANTERN_BENCH_STUB="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--seqs-per-gpu", "8"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--seqs-per-gpu", "8", "--full"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -164,10 +164,10 @@ def test_bench_c5_eight_stub_ranks():
 
 @pytest.mark.timeout(600)
 def test_bench_eight_stub_ranks_print_both_scaling_forms():
-    """The driver's N = 8 invocation (`bench.py --gpus 8 --steps K --warmup W`, nothing else): `value` is the weak-scaling figure (64 per GPU) and
+    """The N = 8 invocation with --full (`bench.py --gpus 8 --steps K --warmup W --full`): `value` is the weak-scaling figure (64 per GPU) and
     `c5_strong` BASELINE's form (64 in all = 8 per GPU, node-parallel evaluate_posterior, <= 2 stream groups), each from its own timed region."""
     import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--full"],
                        env=_stub_env(), capture_output=True, text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -233,12 +233,12 @@ def _stub_env():
 @pytest.mark.timeout(300)
 def test_bench_stdout_is_one_compact_parseable_line(tmp_path):
     """The driver parses bench.py's stdout (and keeps an 8 KB tail of it): stdout must be exactly ONE json line, well under 8 KB,
-    carrying `roofline` and `cpu_baseline`; the extra runs (here: the stub's padding, ~16 KB) go to --extras-out and stderr."""
+    carrying `roofline` and `cpu_baseline` (--full); the extra runs (here: the stub's padding, ~16 KB) go to --extras-out and stderr."""
     import subprocess
     extras = tmp_path / "extras.json"
     for gpus in ("1", "2"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", gpus, "--steps", "3", "--warmup", "1", "--dist-backend", "gloo",
-                            "--extras-out", str(extras)], env=_stub_env(), capture_output=True, text=True, timeout=240)
+                            "--extras-out", str(extras), "--full"], env=_stub_env(), capture_output=True, text=True, timeout=240)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [l for l in r.stdout.splitlines() if l.strip()]
         assert len(lines) == 1 and len(lines[0]) < 8192
@@ -266,3 +266,26 @@ def test_compact_line_of_a_real_report_stays_small():
     assert back["cpu_baseline"]["kind"] == "port" and back["cpu_baseline"]["matches_gpu_token_stream"] is True
     assert back["value"] == full["value"] and back["ms_per_step"] == full["ms_per_step"]          # the headline pair keeps full precision
     assert abs(back["extras"]["mirror_generate_us_per_verify_step"] / full["mirror_generate"]["us_per_verify_step"] - 1) < 1e-5
+
+
+@pytest.mark.timeout(300)
+def test_plain_bench_run_is_the_headline_alone(tmp_path):
+    """Without --full a run times its --steps steps and prints the line, nothing else: no C5 leg, no roofline / CPU baseline / extra runs
+    (stub ranks, N = 1 and 2).  --steps must be at least one."""
+    import subprocess
+    extras = tmp_path / "extras.json"
+    for gpus in ("1", "2"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", gpus, "--steps", "5", "--warmup", "1", "--dist-backend", "gloo",
+                            "--extras-out", str(extras)], env=_stub_env(), capture_output=True, text=True, timeout=240)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["n_gpus"] == int(gpus) and line["steps"] == 5 and line["ms_per_step"] > 0
+        assert line["tokens"] == int(gpus) * 5 * 64 * 2          # exactly --steps steps per rank (64 sequences, the stub's 2 tokens each)
+        for k in ("c5_strong", "roofline", "cpu_baseline", "kernels", "extras"):
+            assert k not in line, k
+        full = json.load(open(extras))
+        assert "ep_batch_sweep" not in full and "configs" not in full
+    bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=_stub_env(), capture_output=True, text=True, timeout=120)
+    assert bad.returncode != 0 and "--steps" in bad.stderr

@@ -27,7 +27,7 @@ def sums(d, pat):
 
 
 out = {"note": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --output-format csv) on the bench command "
-               "itself (`python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --ep-sweep '' --no-extras [flags]`), averaged over "
+               "itself (`python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --ep-sweep '' --no-extras [flags]`), averaged over "
                "every launch of the kernel in the run.  Units: counter value x 1024 bytes.  gfx950 correction (MI355X_MICROARCH.md, HBM): "
                "FETCH_SIZE reports half of the bytes of wide coalesced reads -> doubled; WRITE_SIZE as is.",
        "per_launch": {}, "other_kernels": {}}

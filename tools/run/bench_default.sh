@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/${1:-r2s}
 mkdir -p $OUT
-timeout -k 10 1000 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> $OUT/bench_20_5.err || tail -5 $OUT/bench_20_5.err
+timeout -k 10 1000 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> $OUT/bench_20_5.err || tail -5 $OUT/bench_20_5.err
 python - <<PY
 import json
 d=json.loads(open("$OUT/bench_20_5.json").read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ mkdir -p $O
 i=0
 IFS=";" read -ra FL <<< "${CMP_FLAGS:---spec-rows 3}"; for flags in "${FL[@]}"; do
   i=$((i+1))
-  timeout -k 10 300 python3 bench.py --steps 200 --warmup 20 --cpu-seconds 0 --ep-sweep "" --no-extras $flags > $O/b_$i.json 2> $O/b_$i.err || tail -3 $O/b_$i.err
+  timeout -k 10 300 python3 bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 --ep-sweep "" --no-extras $flags > $O/b_$i.json 2> $O/b_$i.err || tail -3 $O/b_$i.err
   python3 - <<PY
 import json
 d=json.loads(open("$O/b_$i.json").read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ O=gpurun_out/full
 mkdir -p $O
 timeout -k 10 900 python3 -m pytest tests -x -q -m gpu > $O/t_all.txt 2>&1 || { tail -40 $O/t_all.txt; exit 1; }
 tail -2 $O/t_all.txt
-timeout -k 10 1000 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -5 $O/bench.err
+timeout -k 10 1000 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -5 $O/bench.err
 python3 - <<'PY'
 import json
 d=json.loads(open("gpurun_out/full/bench.json").read().strip().splitlines()[-1])

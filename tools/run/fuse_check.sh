@@ -5,10 +5,10 @@ mkdir -p $OUT
 timeout -k 10 600 python -m pytest tests/test_gpu_loop.py tests/test_gpu_window.py -x -q -m gpu > $OUT/tests.log 2>&1
 tail -4 $OUT/tests.log
 for g in 1 2 3; do
-  timeout -k 10 300 python bench.py --steps 100 --warmup 10 --cpu-seconds 0 --ep-sweep "" --no-extras --fuse-o7 --groups $g > $OUT/b_fuse_g$g.json 2> $OUT/b_fuse_g$g.err || tail -3 $OUT/b_fuse_g$g.err
+  timeout -k 10 300 python bench.py --full --steps 100 --warmup 10 --cpu-seconds 0 --ep-sweep "" --no-extras --fuse-o7 --groups $g > $OUT/b_fuse_g$g.json 2> $OUT/b_fuse_g$g.err || tail -3 $OUT/b_fuse_g$g.err
 done
-timeout -k 10 300 python bench.py --steps 100 --warmup 10 --cpu-seconds 6 --ep-sweep "" --no-extras --fuse-o7 --groups 2 --no-events > $OUT/b_fuse_g2_cpu.json 2>/dev/null
-timeout -k 10 300 python bench.py --steps 100 --warmup 10 --cpu-seconds 0 --ep-sweep "" --no-extras > $OUT/b_plain_g1.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --steps 100 --warmup 10 --cpu-seconds 6 --ep-sweep "" --no-extras --fuse-o7 --groups 2 --no-events > $OUT/b_fuse_g2_cpu.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --steps 100 --warmup 10 --cpu-seconds 0 --ep-sweep "" --no-extras > $OUT/b_plain_g1.json 2>/dev/null
 python - <<PY
 import json,glob
 for f in sorted(glob.glob('$OUT/b_*.json')):

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for g in 1 2 4; do
   O=gpurun_out/gprof/g$g; mkdir -p $O
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o s -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --ep-sweep "" --no-extras --extras-out "" --groups $g > $O/line.json 2> $O/err.txt || { tail -5 $O/err.txt; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o s -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --ep-sweep "" --no-extras --extras-out "" --groups $g > $O/line.json 2> $O/err.txt || { tail -5 $O/err.txt; exit 1; }
   rm -f $O/s_kernel_trace.csv $O/s_agent_info.csv
   python3 - <<PY
 import csv, json

@@ -3,7 +3,7 @@ O=gpurun_out/groups
 mkdir -p $O
 for cfg in "63 3 nodes" "64 4 nodes" "64 4 chain" "48 3 nodes" "48 3 chain"; do
   set -- $cfg
-  timeout -k 10 400 python3 bench.py --gpus 1 --steps 200 --warmup 20 --seqs-per-gpu $1 --groups $2 --ep $3 --cpu-seconds 0 --ep-sweep "" --no-extras > $O/n$1g$2$3.json 2> $O/n$1g$2$3.err || { tail -5 $O/n$1g$2$3.err; continue; }
+  timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 200 --warmup 20 --seqs-per-gpu $1 --groups $2 --ep $3 --cpu-seconds 0 --ep-sweep "" --no-extras > $O/n$1g$2$3.json 2> $O/n$1g$2$3.err || { tail -5 $O/n$1g$2$3.err; continue; }
   python3 - <<PY
 import json
 d=json.loads(open("$O/n$1g$2$3.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ timeout -k 10 1000 python3 -m pytest tests -x -q -m gpu > $O/t.txt 2>&1 || { tai
 tail -2 $O/t.txt
 timeout -k 10 200 python3 tools/o7_parts.py 64 2>&1 | grep -v amdgpu | tee $O/parts.txt
 for i in 1 2 3; do
-  timeout -k 10 300 python3 bench.py --steps 200 --warmup 20 --cpu-seconds 0 --ep-sweep "" --no-extras > $O/b_$i.json 2> $O/b_$i.err || { tail -5 $O/b_$i.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 --ep-sweep "" --no-extras > $O/b_$i.json 2> $O/b_$i.err || { tail -5 $O/b_$i.err; exit 1; }
   python3 - <<PY
 import json
 d=json.loads(open("$O/b_$i.json").read().strip().splitlines()[-1])

@@ -7,8 +7,8 @@ A="SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_INS
 B="SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_LDS"
 timeout -k 10 200 rocprofv3 --kernel-trace --pmc $A --output-format csv -d $O/o7_a -o a -- python3 tools/o7_only.py 64 > $O/o7_a.txt 2>&1 &&
 timeout -k 10 200 rocprofv3 --kernel-trace --pmc $B --output-format csv -d $O/o7_b -o b -- python3 tools/o7_only.py 64 > $O/o7_b.txt 2>&1 &&
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc $A --output-format csv -d $O/bench_a -o a -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --ep-sweep "" --no-extras > $O/bench_a.txt 2>&1 &&
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc $B --output-format csv -d $O/bench_b -o b -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --ep-sweep "" --no-extras > $O/bench_b.txt 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc $A --output-format csv -d $O/bench_a -o a -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --ep-sweep "" --no-extras > $O/bench_a.txt 2>&1 &&
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc $B --output-format csv -d $O/bench_b -o b -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --ep-sweep "" --no-extras > $O/bench_b.txt 2>&1
 {
   echo "# rocprofv3 --pmc SQ counters, per launch (sums over all XCDs / CUs), commit $(cat tools/run/.commit 2>/dev/null)"
   echo "## cfg_window_bf16_kernel, 1664 rows (tools/o7_only.py 64)"; python3 tools/pmc_sum.py $O/o7_a cfg_window_bf16; python3 tools/pmc_sum.py $O/o7_b cfg_window_bf16

@@ -10,7 +10,7 @@ for B in 4096 512; do
   bash tools/run/ep_sweep_prof.sh r04_sw$B $B 5 > $O/sw$B.txt 2>&1 || { tail -20 $O/sw$B.txt; exit 1; }
   head -3 gpurun_out/r04_sw$B/summary.txt
 done
-timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

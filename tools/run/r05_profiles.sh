@@ -13,7 +13,7 @@ for B in 4096 512; do
   head -3 gpurun_out/r05_sw$B/summary.txt
   python3 tools/prune_prof.py gpurun_out/r05_sw$B; rm -f gpurun_out/r05_sw$B/stats/*kernel_trace.csv
 done
-timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --extras-out $O/bench_full.json > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --extras-out $O/bench_full.json > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

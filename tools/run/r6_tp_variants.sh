@@ -16,6 +16,6 @@ for r in d["sweep"]:
 PY
 done; done
 for sr in ${SRS:-3 4 5 6 8}; do
-  timeout -k 10 300 python3 bench.py --steps 200 --warmup 20 --cpu-seconds 0 --ep-sweep "" --no-extras --spec-rows $sr > $O/sr_$sr.json 2> $O/sr_$sr.err || { tail -5 $O/sr_$sr.err; continue; }
+  timeout -k 10 300 python3 bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 --ep-sweep "" --no-extras --spec-rows $sr > $O/sr_$sr.json 2> $O/sr_$sr.err || { tail -5 $O/sr_$sr.err; continue; }
   python3 -c "import json; d=json.load(open('$O/sr_$sr.json')); print('spec-rows $sr: us/step %.2f value %.0f' % (1e3*d['ms_per_step'], d['value']), {k: round(1e3*v['avg_launch_ms'],1) for k,v in d.get('kernels',{}).items()}, round(1e3*d['roofline']['avg_launch_ms'],1))"
 done

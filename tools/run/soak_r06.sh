@@ -28,6 +28,6 @@ t0 = time.time()
 T._llamagen_dynamic_loop(False, 1, 0, 1.0, n_seq=1056, steps=5, every=6)
 print(f"LlamaGen two-per-CU instance: 1056 sequences x 5 steps, 176 sequences replayed by the oracle: identical ({time.time() - t0:.0f}s)", flush=True)
 PY
-timeout -k 10 600 python3 bench.py --steps 400 --warmup 20 --cpu-seconds 40 --ep-sweep "" --no-extras --commit-window 1 > $O/turn400.json 2> $O/turn400.err; echo "bench exit $?"
+timeout -k 10 600 python3 bench.py --full --steps 400 --warmup 20 --cpu-seconds 40 --ep-sweep "" --no-extras --commit-window 1 > $O/turn400.json 2> $O/turn400.err; echo "bench exit $?"
 python3 -c "import json; d=json.load(open('$O/turn400.json')); c=d['cpu_baseline']; print('turn-taking, 400 steps: us/step %.2f; oracle replay: %s, mismatches %d (%s)' % (1e3*d['ms_per_step'], c['matches_gpu_token_stream'], c['mismatches'], c['sample']))"
 } | tee $O/soak.txt

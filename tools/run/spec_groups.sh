@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/${1:-r2sg}
 mkdir -p $OUT
 for g in 3 4; do for k in 3 5 8 12 16; do
-  timeout -k 10 300 python bench.py --steps 200 --warmup 20 --cpu-seconds 0 --ep-sweep "" --no-extras --groups $g --spec-rows $k > $OUT/b_g${g}_s$k.json 2> $OUT/b_g${g}_s$k.err || tail -3 $OUT/b_g${g}_s$k.err
+  timeout -k 10 300 python bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 --ep-sweep "" --no-extras --groups $g --spec-rows $k > $OUT/b_g${g}_s$k.json 2> $OUT/b_g${g}_s$k.err || tail -3 $OUT/b_g${g}_s$k.err
 done; done
 python - <<PY
 import json,glob

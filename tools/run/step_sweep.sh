@@ -9,7 +9,7 @@ for ep in nodes chain; do for g in 1 2 4; do
   timeout -k 10 300 python bench.py --steps 100 --warmup 10 --cpu-seconds 0 --ep-sweep "" --no-extras --ep $ep --groups $g --no-events > $OUT/b_${ep}_g$g.json 2> $OUT/b_${ep}_g$g.err || tail -3 $OUT/b_${ep}_g$g.err
 done; done
 timeout -k 10 300 python bench.py --steps 100 --warmup 10 --cpu-seconds 0 --ep-sweep "" --no-extras --ep chain --groups 2 --no-events --python-launch > $OUT/b_chain_g2_py.json 2>/dev/null
-timeout -k 10 300 python bench.py --steps 100 --warmup 10 --cpu-seconds 8 --ep-sweep "" --no-extras --ep nodes --groups 2 > $OUT/b_nodes_g2_cpu.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --steps 100 --warmup 10 --cpu-seconds 8 --ep-sweep "" --no-extras --ep nodes --groups 2 > $OUT/b_nodes_g2_cpu.json 2>/dev/null
 python - <<PY
 import json,glob
 for f in sorted(glob.glob('$OUT/b_*.json')):
