@@ -23,7 +23,8 @@ import torch.nn as nn
 from . import ops
 from .drafters.choices import mc_sim_7b_63, naive_extend_57  # noqa: F401
 from .drafters.kv_cache import initialize_past_key_values
-from .verify import (NodeLogits, ProcessorSpec, WindowRows, UniformFifo, as_rows, concat_original_prob, generate_tree_buffers,
+from .one_call_step import MAX_DEPTH, MAX_ROWS, OneCallStep, slabs_alike
+from .verify import (MirrorBase, NodeLogits, ProcessorSpec, WindowRows, UniformFifo, as_rows, concat_original_prob, generate_tree_buffers,
                      prepare_logits_processor)
 
 
@@ -35,7 +36,7 @@ def cfg_logit_process(combined_logits, cfg_scale=4.0):
     return out.to(combined_logits.dtype)
 
 
-class EaModel(nn.Module):
+class EaModel(MirrorBase, nn.Module):
     # per-model constants: LlamaGen has V == K and no offset
     image_token_offset = 0
     image_lo, image_hi = 0, 2 ** 31 - 1
@@ -78,11 +79,6 @@ class EaModel(nn.Module):
         self.base_model.model.tree_mode = True
         self.base_model.model.tree_mask = None
 
-    def _uniforms(self) -> UniformFifo:
-        if self._fifo is None:
-            self._fifo = UniformFifo(self.nearest_latents.device, window=self.uniform_window)
-        return self._fifo
-
     def _ep_config(self, static: bool, proc: ProcessorSpec, lantern, lantern_k, lantern_delta) -> ops.EpConfig:
         return ops.EpConfig(mode=ops.MODE_STATIC_LG if static else ops.MODE_DYNAMIC, tok_offset=self.image_token_offset,
                             img_lo=self.image_lo, img_hi=self.image_hi, lantern=bool(lantern), k=int(lantern_k),
@@ -111,16 +107,8 @@ class EaModel(nn.Module):
 
     def tree_decoding(self, tree_candidates, past_key_values, tree_position_ids, input_ids, retrieve_indices, cfg_scale,
                       attention_mask=None, input_position_diff=0):
-        position_ids = tree_position_ids + input_ids.shape[1]
-        if self.mask_non_image:      # Anole: separate cond / uncond position ids (ea_model_anole.py:915-918)
-            position_ids = position_ids.unsqueeze(0)
-            position_ids = torch.cat([position_ids, position_ids - input_position_diff], dim=0)
-        if attention_mask is not None:
-            remaining = input_ids.shape[1] + tree_candidates.shape[1] - attention_mask.shape[1]
-            attention_mask = torch.cat([attention_mask, torch.ones((attention_mask.shape[0], remaining), dtype=torch.long,
-                                                                    device=attention_mask.device)], dim=1)
-        outputs, tree_logits, hidden_state = self(input_ids=tree_candidates, output_orig=True, past_key_values=past_key_values,
-                                                  position_ids=position_ids, attention_mask=attention_mask)
+        outputs, tree_logits, hidden_state = self._tree_forward(tree_candidates, past_key_values, tree_position_ids, input_ids, attention_mask,
+                                                                input_position_diff)
         half = tree_logits.shape[0] // 2
         proc = self._active_proc
         if self.kernel_set == "window" and proc is not None:
@@ -167,7 +155,7 @@ class EaModel(nn.Module):
         out = ops.evaluate_posterior_window(cfg_w, logits.V, logits.win[None], logits.win_lo, logits.row_index(), candidates[None], fifo.buf,
                                             row_hot=logits.row_hot[None], table=self._packed_table(int(lantern_k)) if lantern else None,
                                             aux=aux, cursor=fifo.cursor, want_dense=True, want_window=False, rows_probs=True)
-        if int(out["counters"][0, 5]) in (2, 6, 7, 8) and logits.dense_source is not None:
+        if int(out["counters"][0, 5]) in self._RETRY_DENSE and logits.dense_source is not None:
             # a state only the dense kernel represents (the residual vanished, staging limits): the same step on the dense HIP
             # kernel -- processors applied per visited row there -- from the same position of the uniform stream
             fifo.cursor.copy_(cur0)
@@ -178,15 +166,6 @@ class EaModel(nn.Module):
             return best[0].to(torch.int64), int(alen[0]), sample_p[0]
         ops.raise_on_status(out["counters"])
         return out["best"][0].to(torch.int64), int(out["accept_len"][0]), out["sample_p"][0]
-
-    def _packed_table(self, k: int) -> torch.Tensor:
-        cols = -(-(k + 1) // 8) * 8
-        if cols > min(1024, self.nearest_latents.shape[1]):
-            return self.nearest_latents
-        cache = self.__dict__.setdefault("_packed_tables", {})
-        if cols not in cache:
-            cache[cols] = ops.pack_vq_table(self.nearest_latents, cols)
-        return cache[cols]
 
     # ------------------------------------------------------------------ O8 static, :464-669
     def evaluate_posterior_v1(self, logits, candidates, logits_processor, cart_candidates_prob, op, p_indices, tree_candidates,
@@ -263,8 +242,6 @@ class EaModel(nn.Module):
     # target calls and both RNG positions), organised for the device: a step's verdict -- best path, accept length, status -- stays in
     # HBM and feeds the KV move, the accepted-hidden gather and the bonus-token draw there; the host reads ONE packed 4-int record per
     # step (it needs the accept length to slice the drafter's inputs), where the reference syncs on every tried candidate.
-    _RETRY_DENSE = (2, 6, 7, 8)
-
     def _posterior_on_device(self, rows, candidates, logits_processor, aux, static, lantern, lantern_k, lantern_delta, u):
         """O8 (+ the bonus-token draw when the windowed kernel does it) with every result left on the device:
         dict(best [1] i32, accept_len [1] i32, status [1] i32, token [1] i64 or None, sample_p [V] f32 or None)."""
@@ -298,274 +275,106 @@ class EaModel(nn.Module):
     native_step = True          # False: every kernel its own ctypes call with fresh tensors (the form the one-call step is tested against)
 
     def _native_ctx(self, st, logits_processor, cfg_scale, lantern, lantern_k, lantern_delta):
-        """What a generate() call's static-tree steps share, built once (ea_model_lumina_mgpt.EaLumina_mGPT._native_ctx is the same idea): the
-        lantern_step_group with preallocated outputs.  None when this configuration stays on the per-kernel path (dynamic trees, greedy decoding,
-        the dense kernel set, a model spread over devices, slabs of different shapes)."""
-        import ctypes as C
-        from . import _lib
+        """What a generate() call's steps share, built once: the one_call_step.OneCallStep with its preallocated outputs and -- here -- the KV length
+        double buffer.  None when this configuration stays on the per-kernel path (the dense kernel set with sampling, a model spread over
+        devices, slabs of different shapes, a tree or a window beyond what one group takes)."""
         greedy = logits_processor is None          # temperature <= 1e-5: the greedy / TVD accept as the call's O8 stage (lantern_step_greedy)
-        if not (self.native_step and (self.kernel_set == "window" or greedy) and not st.multi_device):
+        if not (self.native_step and (self.kernel_set == "window" or greedy) and not st.multi_device and slabs_alike(st.slabs)):
             return None
-        s0 = st.slabs[0]
-        if any(x.shape != s0.shape or x.dtype != s0.dtype or x.device != s0.device or not x.is_contiguous() for x in st.slabs):
-            return None
-        dev = s0.device
+        dev = st.slabs[0].device
+        tree = None
         if st.static:
             tb, hip = self.tree_buffers, self.tree_buffers["_hip"]
             N, P, D, R = hip["N"], hip["P"], hip["D"], hip["R"]
+            tree = dict(hip, tree_indices=tb["tree_indices"], retrieve=tb["retrieve_indices_head"])
         else:          # EAGLE-2: the drafter hands over a tree per step (token list, paths); P and D are that step's, N = its token count
             N, P, D, R = int(st.draft_tokens.shape[1]), 0, 0, 0
         V = self.vocab_size
-        lo, W = (self.image_lo, self.image_hi - self.image_lo) if self.mask_non_image else (0, V)
-        if D > 8 or N > 64 or W % 8 or W > 16384:
+        lo, hi = (self.image_lo, self.image_hi) if self.mask_non_image else (0, V)
+        if D > MAX_DEPTH or N > MAX_ROWS or (hi - lo) % 8 or hi - lo > 16384:
             return None
         proc = ProcessorSpec.from_hf(logits_processor) if not greedy else ProcessorSpec()
-        nx = types.SimpleNamespace(C=C, L=_lib.lib(), dev=dev, N=N, P=P, D=D, R=R, lo=lo, W=W, static=bool(st.static), greedy=greedy)
-        z = lambda *shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        nx.cand, nx.cart, nx.tcand = z(1, max(P, 1), max(D, 1), dt=torch.int64), z(1, max(P, 1), max(D, 1), dt=torch.float32), z(1, N, dt=torch.int64)
-        nx.win, nx.hot = z(N, W, dt=torch.float32), z(N, dt=torch.int32)
-        # the verdict record, double-buffered: best, accept_len, counters[6], bonus token (int64 at words 8-9)
-        nx.recs = [z(16, dt=torch.int32), z(16, dt=torch.int32)]
-        nx.toks = [r_[8:10].view(torch.int64) for r_ in nx.recs]
-        nx.otok, nx.omass = z(1, dt=torch.int32), z(1, dt=torch.float32)
-        nx.out_hs, nx.acc = [None, None], z(1, 8, dt=torch.int64)
-        nx.stream = torch.cuda.current_stream().cuda_stream
-        if st.static:
-            nx.tree_indices = tb["tree_indices"].to(dev).contiguous()
-            nx.retrieve = tb["retrieve_indices_head"].to(dev).contiguous()
-            ri = nx.retrieve.clone()
-            ri[ri < 0] += N
-            nx.row_index = ri.to(torch.int32).contiguous()
-        n_sl = len(st.slabs)
-        nx.prev = [torch.zeros(n_sl, dtype=torch.int64, device=dev), torch.zeros(n_sl, dtype=torch.int64, device=dev)]
-        nx.parity = 0
-        g = nx.group = (_lib.StepGroup * 1)()
-        a = g[0]
-        if st.static:
-            a.tree_indices, a.retrieve = nx.tree_indices.data_ptr(), nx.retrieve.data_ptr()
-        a.B, a.n_flat, a.N, a.P, a.D = 1, 0, N, P, D          # (n_flat: set per step from the drafter's sample list; dynamic trees: P, D per step)
-        a.tree_cand, a.cand, a.cart_prob = nx.tcand.data_ptr(), nx.cand.data_ptr(), nx.cart.data_ptr()
-        a.V, a.cfg, a.model = V, float(cfg_scale), (ops.MODEL_ANOLE if self.mask_non_image else ops.MODEL_PLAIN)
-        a.img_lo, a.img_hi = (self.image_lo, self.image_hi) if self.mask_non_image else (0, V)
-        a.top_k, a.win_lo, a.win_len, a.out_kind = min(proc.top_k, V), lo, W, ops.ROWS_PROBS
-        a.out_win, a.row_hot, a.temperature, a.top_p = nx.win.data_ptr(), nx.hot.data_ptr(), float(proc.temperature), float(proc.top_p)
-        if greedy:
-            # the dense f32 rows of the O7 stage, the accepted row, the scratch of the (path, depth) cells (sized for any tree the context takes)
-            nx.g_logits, nx.g_out, nx.g_ok = z(max(N, 64), V, dt=torch.float32), z(1, V, dt=torch.float32), z(64 * 8, dt=torch.int32)
-            nx.g_table = self.nearest_latents.contiguous() if lantern else None
-            q = nx.gq = _lib.StepGreedy()
-            q.logits, q.out_row, q.ok_scratch = nx.g_logits.data_ptr(), nx.g_out.data_ptr(), nx.g_ok.data_ptr()
-            q.lantern, q.k, q.delta, q.tok_offset = int(bool(lantern)), int(lantern_k), float(lantern_delta), int(self.image_token_offset)
-            if nx.g_table is not None:
-                q.nn_table = nx.g_table.data_ptr()
-                q.table_rows, q.table_cols = nx.g_table.shape
-            q.win_lo, q.win_len = lo, W
-            if st.static:
-                q.row_index = nx.row_index.data_ptr()
-            a.greedy = C.pointer(q)
-            a.out_win, a.top_k = None, 0
-        cfg = self._ep_config(bool(st.static), proc, lantern, lantern_k, lantern_delta)
-        p = a.ep
-        p.B, p.P, p.D, p.V, p.rows_per_seq = 1, P, D, V, N
-        p.mode, p.syntax_shortcut, p.tok_offset = cfg.mode, int(cfg.syntax_shortcut), cfg.tok_offset
-        p.img_lo, p.img_hi, p.n_syntax = cfg.img_lo, min(cfg.img_hi, 2 ** 31 - 1), len(cfg.syntax)
-        for i, sx in enumerate(cfg.syntax):
-            p.syntax[i] = int(sx)
-        p.lantern, p.k, p.delta = int(cfg.lantern), int(cfg.k), float(cfg.delta)
-        p.top_k, p.temperature, p.top_p = 0, 1.0, 1.0          # the rows are final probabilities (the processors ran in the O7 stage)
-        fifo = None if greedy else self._uniforms()          # (greedy decoding draws nothing: the Python RNG stays where the reference leaves it)
-        p.n_uniforms, p.R, p.N, p.row_index_per_seq = (0 if greedy else fifo.buf.shape[1]), R, N, 0
-        nx.table = self._packed_table(int(lantern_k)) if lantern else None
-        if nx.table is not None:
-            p.table_rows, p.table_cols = nx.table.shape
-        b = a.ep_buf
-        b.logits = nx.win.data_ptr()
-        if st.static:
-            b.row_index, b.cand, b.cart_prob = nx.row_index.data_ptr(), nx.cand.data_ptr(), nx.cart.data_ptr()
-            b.op_off, b.p_idx, b.b_off, b.b_idx = hip["op_off"].data_ptr(), hip["p_idx"].data_ptr(), hip["b_off"].data_ptr(), hip["b_idx"].data_ptr()
-            b.tree_cand = nx.tcand.data_ptr()
-        b.nn_table = nx.table.data_ptr() if nx.table is not None else None
-        if not greedy:
-            b.uniforms, b.cursor = fifo.buf.data_ptr(), fifo.cursor.data_ptr()
-        w = a.ep_win
-        w.win_lo, w.win_len, w.row_hot, w.rows_kind = lo, W, nx.hot.data_ptr(), ops.ROWS_PROBS
-        w.orig_prob_stride, w.orig_prob_offset = V, lo
-        w.out_tok, w.out_mass = nx.otok.data_ptr(), nx.omass.data_ptr()
-        a.slab_ptrs, a.slab_seq = st.slab_ptrs.data_ptr(), st.slab_seq.data_ptr()
-        S, d = s0.shape[-2], s0.shape[-1]
-        a.n_slabs, a.elem_bytes, a.outer, a.S_max, a.d = n_sl, s0.element_size(), s0.numel() // (S * d), S, d
-        a.accepted_tokens = nx.acc.data_ptr()
-        a.hid_groups = 2
+        nx = OneCallStep(st.slabs, st.slab_ptrs, st.slab_seq, N=N, P=P, D=D, R=R, V=V, win_lo=lo, win_len=hi - lo,
+                         ep_cfg=self._ep_config(bool(st.static), proc, lantern, lantern_k, lantern_delta),
+                         model=ops.MODEL_ANOLE if self.mask_non_image else ops.MODEL_PLAIN, cfg_scale=cfg_scale, top_k=min(proc.top_k, V),
+                         temperature=proc.temperature, top_p=proc.top_p, img_lo=lo, img_hi=hi,
+                         fifo=None if greedy else self._uniforms(),          # (greedy decoding draws nothing: the Python RNG stays where the reference leaves it)
+                         table=self._packed_table(int(lantern_k)) if lantern else None, tree=tree,
+                         greedy=dict(lantern=lantern, k=lantern_k, delta=lantern_delta, tok_offset=self.image_token_offset,
+                                     table=self.nearest_latents.contiguous() if lantern else None) if greedy else None)
+        st.native_prev = [torch.zeros(len(st.slabs), dtype=torch.int64, device=dev) for _ in range(2)]
         return nx
 
     def _verify_step_native(self, st, nx, logits_processor, cfg_scale, lantern, lantern_k, lantern_delta):
-        """One static-tree step: generate_candidates (one call: the target forward needs the tree tokens), the forward, then ONE lantern_verify_step
-        call -- Temperature -> TopP -> TopK + softmax of all rows, evaluate_posterior with the bonus draw, the KV /
-        hidden / token commit (only where the walk reported no status) -- on preallocated buffers, and one host read of the verdict record.  Same
-        kernels, same uniforms, same results as the per-kernel path (tests/test_gpu_generate_lg.py runs the reference-recorded cases through both)."""
-        if not nx.static:
-            return self._verify_step_native_dynamic(st, nx, logits_processor, cfg_scale, lantern, lantern_k, lantern_delta)
-        C, L, a = nx.C, nx.L, nx.group[0]
-        tl = st.tree_logits
-        ss_token = tl[0].to(nx.dev).contiguous()
-        ss_prob = None
-        if not nx.greedy:
-            ss_prob = tl[1].to(nx.dev)
-            ss_prob = (ss_prob if ss_prob.dtype == torch.float32 else ss_prob.float()).contiguous()
-        sample = st.sample_token.to(nx.dev).reshape(-1)[:1].contiguous()
-        par = nx.parity
-        rec, tokbuf = nx.recs[par], nx.toks[par]
-        a.ep_buf.best, a.ep_buf.accept_len, a.ep_buf.counters = rec.data_ptr(), rec.data_ptr() + 4, rec.data_ptr() + 8
-        a.ep_win.token = tokbuf.data_ptr()
-        a.stream, a.ss_token = nx.stream, None          # (ss_token NULL: lantern_verify_step takes the candidates as the call below leaves them)
-        a.flags = ops._lib.STEP_CANDIDATES_READY
-        ops.check(L.lantern_gather_candidates(C.c_void_p(ss_token.data_ptr()), C.c_void_p(ss_prob.data_ptr() if ss_prob is not None else None), C.c_void_p(sample.data_ptr()),
-                                              C.c_void_p(a.tree_indices), C.c_void_p(a.retrieve), 1, ss_token.numel(), nx.N, nx.P, nx.D, C.c_void_p(a.tree_cand),
-                                              C.c_void_p(a.cand), C.c_void_p(a.cart_prob if ss_prob is not None else None), C.c_void_p(nx.stream)), "gather_candidates")
+        """One step through ONE lantern_verify_step call -- Temperature -> TopP -> TopK + softmax of all rows, evaluate_posterior with the bonus draw, the
+        KV / hidden / token commit (only where the walk reported no status) -- on preallocated buffers, and one host read of the verdict record.  Same
+        kernels, same uniforms, same results as the per-kernel path (tests/test_gpu_generate_lg.py runs the reference-recorded cases through both).
+        The two tree kinds differ in how the tree and the candidates arrive.  Static: generate_candidates is one call before the forward (the target
+        needs the tree tokens).  EAGLE-2 (the reference's default for LlamaGen / Anole): the tree comes from the drafter with its token list, so the
+        candidates are one gather here (ea_model_llamagen.py:1125-1131) and the step runs on this step's paths.  None: a tree outside what the step
+        holds (more rows than it was built for, depth > 8) -- the caller takes the per-kernel path for this step."""
+        greedy = logits_processor is None
+        if st.static:
+            tl = st.tree_logits
+            nx.begin()
+            nx.gather_candidates(tl[0], None if greedy else tl[1], st.sample_token)
+            tokens, position_ids, retrieve, candidates = nx.tcand, self.tree_buffers["tree_position_ids"], nx.retrieve, nx.cand[0]
+        else:
+            retrieve = st.retrieve_indices.to(nx.dev)
+            if retrieve.dtype != torch.int64:
+                retrieve = retrieve.to(torch.int64)
+            retrieve = retrieve.contiguous()
+            candidates = torch.cat((st.draft_tokens, st.padding), dim=1)[0, retrieve].to(nx.dev).contiguous()          # [P, D] i64, -1 behind a path's end
+            if not nx.bind_tree(retrieve, candidates, int(st.draft_tokens.shape[1])):
+                return None
+            self.base_model.model.tree_mask = st.tree_mask
+            nx.begin()
+            tokens, position_ids = st.draft_tokens, st.tree_position_ids
         kw = dict(input_position_diff=st.input_position_diff) if self.mask_non_image else {}
-        tree_candidates = torch.cat([nx.tcand, nx.tcand])
-        _, tree_logits, hidden_new = self._tree_forward(tree_candidates, self.base_model.past_key_values, self.tree_buffers["tree_position_ids"], st.input_ids,
+        _, tree_logits, hidden_new = self._tree_forward(torch.cat([tokens, tokens]), self.base_model.past_key_values, position_ids, st.input_ids,
                                                         st.attention_mask, **kw)
         half = tree_logits.shape[0] // 2
-        cl, ul = tree_logits[0], tree_logits[half]
-        if cl.dtype not in (torch.bfloat16, torch.float32):
-            cl, ul = cl.float(), ul.float()
-        cl, ul = cl.contiguous(), ul.contiguous()
-        a.cond, a.uncond, a.dtype = cl.data_ptr(), ul.data_ptr(), int(cl.dtype == torch.bfloat16)
-        if not nx.greedy:
-            orig = concat_original_prob(tl[2])
-            a.ep_buf.orig_prob = orig.data_ptr()
-        hid = hidden_new.contiguous()[None]                                                # [1, 2, N, H]
-        out_h = nx.out_hs[par]
-        if out_h is None or out_h.dtype != hid.dtype or out_h.shape[-1] != hid.shape[-1]:
-            out_h = nx.out_hs[par] = torch.zeros((1, 2, nx.D, hid.shape[-1]), dtype=hid.dtype, device=nx.dev)
-        a.hidden, a.out_hidden, a.hid_elem_bytes, a.H = hid.data_ptr(), out_h.data_ptr(), hid.element_size(), hid.shape[-1]
-        if nx.greedy:          # no uniforms, no counters: the record's counter words stay zero
-            a.ep_buf.counters = None
-            nx.gq.token = tokbuf.data_ptr()
-        else:
+        nx.bind_rows(tree_logits[0], tree_logits[half])
+        if st.static and not greedy:
+            nx.bind_orig_prob(tl[2])
+        out_h = nx.bind_hidden(hidden_new[None])                                           # [1, 2, N, H]
+        if not greedy:
             fifo = self._uniforms()
             fifo.reserve(nx.P * nx.D)
             u = torch.rand(1, dtype=torch.float64, device=nx.dev)
-            a.ep_win.u_bonus = u.data_ptr()
+            nx.bind_bonus(u)
         prev = st.input_ids.shape[1]
-        cur, nxt = nx.prev[par], nx.prev[par ^ 1]
+        cur, nxt = st.native_prev[nx.parity], st.native_prev[nx.parity ^ 1]
         cur.fill_(prev)
-        a.slab_prev, a.new_len = cur.data_ptr(), nxt.data_ptr()
-        ops.check(L.lantern_verify_step(nx.group, 1), "verify_step")
-        r = rec.tolist()                                                                   # the step's one host read
-        best, alen, n_used, status, tok = r[0], r[1], r[5], r[7], r[8]
-        nx.parity ^= 1
+        nx.bind_lengths(cur, nxt)
+        nx.launch()
+        best, alen, n_used, status, tok = nx.verdict()                                     # the step's one host read
+        nx.end()
         if status != 0:
             if status in self._RETRY_DENSE:
                 # a state only the dense kernel represents: nothing was committed (lantern_verify_step commits only walks without a status); the same
                 # step on the dense HIP kernel, from the same uniforms, through the host-integer path (rare: once in millions of steps)
                 fifo.cursor.sub_(n_used)
-                hip = self.tree_buffers["_hip"]
-                aux = ops.StaticAux(cart_prob=nx.cart, orig_prob=orig, op_off=hip["op_off"], p_idx=hip["p_idx"], b_off=hip["b_off"], b_idx=hip["b_idx"],
-                                    tree_cand=nx.tcand[:, :hip["N"]])
-                rows = NodeLogits(self._dense_node_logits(tree_logits, half, cfg_scale), nx.retrieve)
-                ep = self._posterior_on_device(rows, nx.cand[0], logits_processor, aux, True, lantern, lantern_k, lantern_delta, u)
-                ops.raise_on_status(ep["counters"])
-                al, bst = int(ep["accept_len"][0]), int(ep["best"][0])
-                out = self.update_inference_inputs(st.input_ids, nx.cand[0], bst, al, nx.retrieve, logits_processor, 0, st.slabs, self.base_model.current_length_data,
-                                                   hidden_new, ep["sample_p"], cfg_scale, st.input_position_diff, st.attention_mask, True, u=u)
-                st.input_ids = out[0]
-                self._take_draft(st, out[1], out[-1])
-                return bst, al
-            ops.raise_on_status(rec[2:8].reshape(1, 6))
-        n = alen + 1
-        self.base_model.current_length_data.fill_(prev + n)
-        st.input_ids = torch.cat([st.input_ids, nx.acc[:, :n].to(st.input_ids.device)], dim=-1)
-        token = tokbuf.reshape(1, 1)
-        self._take_draft(st, self._draft_next(st.input_ids, out_h[0, :, :n], token, logits_processor, cfg_scale, st.input_position_diff, st.attention_mask, True),
-                         token)
-        return best, alen
-
-    def _verify_step_native_dynamic(self, st, nx, logits_processor, cfg_scale, lantern, lantern_k, lantern_delta):
-        """One EAGLE-2 step (the reference's default for LlamaGen / Anole): the tree arrives from the drafter with its token list, so the candidates are
-        one gather here (ea_model_llamagen.py:1125-1131) and lantern_verify_step runs the row post-process, evaluate_posterior with the bonus draw and
-        the commit on this step's paths (`retrieve` [P, D]; P and D change from step to step, the group's fields follow them).  None: a tree outside
-        what the group holds (more rows than the context was built for, depth > 8) -- the caller takes the per-kernel path for this step."""
-        C, L, a = nx.C, nx.L, nx.group[0]
-        retrieve = st.retrieve_indices.to(nx.dev)
-        if retrieve.dtype != torch.int64:
-            retrieve = retrieve.to(torch.int64)
-        retrieve = retrieve.contiguous()
-        P, D = retrieve.shape
-        N = int(st.draft_tokens.shape[1])
-        if D > 8 or P < 1 or N < 1:
-            return None
-        if N > nx.win.shape[0] and not nx.greedy:          # (a drafter whose trees grow: the row buffers follow)
-            nx.win = torch.zeros((N, nx.W), dtype=torch.float32, device=nx.dev)
-            nx.hot = torch.zeros(N, dtype=torch.int32, device=nx.dev)
-            a.out_win, a.row_hot, a.ep_buf.logits, a.ep_win.row_hot = nx.win.data_ptr(), nx.hot.data_ptr(), nx.win.data_ptr(), nx.hot.data_ptr()
-        nx.N = N
-        a.N, a.ep.rows_per_seq, a.ep.N = N, N, N
-        self.base_model.model.tree_mask = st.tree_mask
-        candidates = torch.cat((st.draft_tokens, st.padding), dim=1)[0, retrieve].to(nx.dev).contiguous()          # [P, D] i64, -1 behind a path's end
-        row_index = torch.where(retrieve < 0, retrieve + nx.N, retrieve).to(torch.int32)
-        kw = dict(input_position_diff=st.input_position_diff) if self.mask_non_image else {}
-        _, tree_logits, hidden_new = self._tree_forward(torch.cat([st.draft_tokens, st.draft_tokens]), self.base_model.past_key_values, st.tree_position_ids,
-                                                        st.input_ids, st.attention_mask, **kw)
-        half = tree_logits.shape[0] // 2
-        cl, ul = tree_logits[0], tree_logits[half]
-        if cl.dtype not in (torch.bfloat16, torch.float32):
-            cl, ul = cl.float(), ul.float()
-        cl, ul = cl.contiguous(), ul.contiguous()
-        par = nx.parity
-        rec, tokbuf = nx.recs[par], nx.toks[par]
-        a.stream, a.ss_token, a.retrieve = nx.stream, None, retrieve.data_ptr()
-        a.flags = ops._lib.STEP_CANDIDATES_READY
-        a.P, a.D, a.ep.P, a.ep.D = P, D, P, D
-        a.cand = candidates.data_ptr()
-        a.cond, a.uncond, a.dtype = cl.data_ptr(), ul.data_ptr(), int(cl.dtype == torch.bfloat16)
-        b = a.ep_buf
-        b.best, b.accept_len, b.counters = rec.data_ptr(), rec.data_ptr() + 4, rec.data_ptr() + 8
-        b.row_index, b.cand = row_index.data_ptr(), candidates.data_ptr()
-        a.ep_win.token = tokbuf.data_ptr()
-        hid = hidden_new.contiguous()[None]                                                # [1, 2, N, H]
-        flat = nx.out_hs[par]
-        if flat is None or flat.dtype != hid.dtype or flat.numel() != 2 * 8 * hid.shape[-1]:
-            flat = nx.out_hs[par] = torch.zeros(2 * 8 * hid.shape[-1], dtype=hid.dtype, device=nx.dev)
-        out_h = flat[:2 * D * hid.shape[-1]].view(1, 2, D, hid.shape[-1])          # (the kernel's [B, G, D, H] layout for THIS step's depth)
-        a.hidden, a.out_hidden, a.hid_elem_bytes, a.H = hid.data_ptr(), out_h.data_ptr(), hid.element_size(), hid.shape[-1]
-        if nx.greedy:
-            if N > nx.g_logits.shape[0] or P * max(D - 1, 1) > nx.g_ok.numel():
-                return None
-            b.counters = None
-            nx.gq.token, nx.gq.row_index = tokbuf.data_ptr(), row_index.data_ptr()
-        else:
-            fifo = self._uniforms()
-            fifo.reserve(P * D)
-            u = torch.rand(1, dtype=torch.float64, device=nx.dev)
-            a.ep_win.u_bonus = u.data_ptr()
-        prev = st.input_ids.shape[1]
-        cur, nxt = nx.prev[par], nx.prev[par ^ 1]
-        cur.fill_(prev)
-        a.slab_prev, a.new_len = cur.data_ptr(), nxt.data_ptr()
-        ops.check(L.lantern_verify_step(nx.group, 1), "verify_step")
-        r = rec.tolist()                                                                   # the step's one host read
-        best, alen, n_used, status, tok = r[0], r[1], r[5], r[7], r[8]
-        nx.parity ^= 1
-        if status != 0:
-            if status in self._RETRY_DENSE:
-                fifo.cursor.sub_(n_used)          # nothing was committed: the same step on the dense HIP kernel, from the same uniforms (host-integer path)
+                aux = None
+                if st.static:
+                    hip = self.tree_buffers["_hip"]
+                    aux = ops.StaticAux(cart_prob=nx.cart, orig_prob=concat_original_prob(tl[2]), op_off=hip["op_off"], p_idx=hip["p_idx"], b_off=hip["b_off"], b_idx=hip["b_idx"],
+                                        tree_cand=nx.tcand[:, :hip["N"]])
                 rows = NodeLogits(self._dense_node_logits(tree_logits, half, cfg_scale), retrieve)
-                ep = self._posterior_on_device(rows, candidates, logits_processor, None, False, lantern, lantern_k, lantern_delta, u)
+                ep = self._posterior_on_device(rows, candidates, logits_processor, aux, st.static, lantern, lantern_k, lantern_delta, u)
                 ops.raise_on_status(ep["counters"])
                 al, bst = int(ep["accept_len"][0]), int(ep["best"][0])
                 out = self.update_inference_inputs(st.input_ids, candidates, bst, al, retrieve, logits_processor, 0, st.slabs, self.base_model.current_length_data,
-                                                   hidden_new, ep["sample_p"], cfg_scale, st.input_position_diff, st.attention_mask, False, u=u)
+                                                   hidden_new, ep["sample_p"], cfg_scale, st.input_position_diff, st.attention_mask, st.static, u=u)
                 st.input_ids = out[0]
-                self._take_draft(st, out[1:5], out[-1])
+                self._take_draft(st, out[1] if st.static else out[1:5], out[-1])
                 return bst, al
-            ops.raise_on_status(rec[2:8].reshape(1, 6))
+            nx.raise_on_status()
         n = alen + 1
         self.base_model.current_length_data.fill_(prev + n)
         st.input_ids = torch.cat([st.input_ids, nx.acc[:, :n].to(st.input_ids.device)], dim=-1)
-        token = tokbuf.reshape(1, 1)
-        self._take_draft(st, self._draft_next(st.input_ids, out_h[0, :, :n], token, logits_processor, cfg_scale, st.input_position_diff, st.attention_mask, False),
+        token = nx.token.reshape(1, 1)
+        self._take_draft(st, self._draft_next(st.input_ids, out_h[0, :, :n], token, logits_processor, cfg_scale, st.input_position_diff, st.attention_mask, st.static),
                          token)
         return best, alen
 

@@ -24,7 +24,8 @@ import torch.nn as nn
 from . import ops
 from .drafters.choices import mc_sim_7b_63
 from .drafters.kv_cache import initialize_past_key_values
-from .verify import WindowRows, NodeLogits, UniformFifo, as_rows, concat_original_prob, generate_tree_buffers  # noqa: F401
+from .one_call_step import MAX_DEPTH, MAX_ROWS, OneCallStep, slabs_alike
+from .verify import MirrorBase, WindowRows, NodeLogits, UniformFifo, as_rows, concat_original_prob, generate_tree_buffers  # noqa: F401
 
 TOPK = 10
 IMAGE_LO, IMAGE_HI = 4, 8196          # image tokens are 4..8195 (ea_model_lumina_mgpt.py:37,322-323)
@@ -66,7 +67,7 @@ class InterleavedTopKLogitsWarper:
         return out.to(scores.dtype)
 
 
-class EaLumina_mGPT(nn.Module):
+class EaLumina_mGPT(MirrorBase, nn.Module):
     uniform_window = 4096     # uniforms staged per refill (verify.UniformFifo)
     # "window": tree rows cross HBM as 8192-wide image-token windows of probabilities, evaluate_posterior keeps the residual
     # distribution in LDS.  "dense": full-vocabulary rows, the reference's intermediate tensors exactly.
@@ -110,22 +111,6 @@ class EaLumina_mGPT(nn.Module):
     def reset_tree_mode(self):
         self.base_model.model.tree_mode = True
         self.base_model.model.tree_mask = None
-
-    def _packed_table(self, k: int) -> torch.Tensor:
-        """Neighbour table in the hot-path layout (16-byte aligned rows of ceil8(k+1) ids, lantern_pack_vq_table), built once per k;
-        tables too narrow to pad (k + 1 > 1024 staged ids is the kernel's limit anyway) are passed through."""
-        cols = -(-(k + 1) // 8) * 8
-        if cols > min(1024, self.nearest_latents.shape[1]):
-            return self.nearest_latents
-        cache = self.__dict__.setdefault("_packed_tables", {})
-        if cols not in cache:
-            cache[cols] = ops.pack_vq_table(self.nearest_latents, cols)
-        return cache[cols]
-
-    def _uniforms(self) -> UniformFifo:
-        if self._fifo is None:
-            self._fifo = UniformFifo(self.nearest_latents.device, window=self.uniform_window)
-        return self._fifo
 
     # ------------------------------------------------------------------ :458-522
     def initialize_tree(self, input_ids, past_key_values, logits_processors, attention_mask=None, tree_attn_mask=None):
@@ -257,9 +242,6 @@ class EaLumina_mGPT(nn.Module):
         best, alen, sample_p, counters = ops.evaluate_posterior(cfg, rows.float()[None], row_index, candidates[None], fifo.buf,
                                                                 table=self.nearest_latents if lantern else None, aux=aux, cursor=fifo.cursor)
         return dict(best=best, accept_len=alen, counters=counters, sample_p=sample_p, token=None)
-
-    # statuses of the windowed kernel the dense kernel does not have (the residual vanished, uniforms / tree beyond its LDS staging)
-    _RETRY_DENSE = (2, 6, 7, 8)
 
     def evaluate_posterior(self, logits, candidates, cart_candidates_prob=None, original_prob=None, p_indices=None,
                            tree_candidates=None, b_indices=None, do_sample=True, lantern=False, lantern_k=1000,
@@ -415,104 +397,31 @@ class EaLumina_mGPT(nn.Module):
     native_step = True          # False: every kernel its own ctypes call with fresh tensors (the form the native step is tested against)
 
     def _native_ctx(self, st, lantern, lantern_k, lantern_delta):
-        """Everything of a generate() call that does not change from step to step, built once: the lantern_step_group with its preallocated outputs
-        (candidates, processed rows, verdict record, accepted hidden states / tokens, the KV length double buffer) and the node tables' workspace.
-        None when this configuration stays on the per-kernel path (dynamic trees, the dense kernel set, slabs of different shapes)."""
-        import ctypes as C
-        from . import _lib
-        if not (self.native_step and st.static and self.kernel_set == "window"):
+        """Everything of a generate() call that does not change from step to step, built once: the one_call_step.OneCallStep with its preallocated
+        outputs (candidates, processed rows, verdict record, accepted hidden states / tokens), the node tables' workspace and -- here -- the KV
+        length double buffer.  None when this configuration stays on the per-kernel path (dynamic trees, the dense kernel set, slabs of different shapes)."""
+        if not (self.native_step and st.static and self.kernel_set == "window" and slabs_alike(st.slabs)):
             return None
         tb, hip = self.tree_buffers, self.tree_buffers["_hip"]
-        s0 = st.slabs[0]
-        if any(x.shape != s0.shape or x.dtype != s0.dtype or x.device != s0.device or not x.is_contiguous() for x in st.slabs):
-            return None
-        dev = s0.device
+        dev = st.slabs[0].device
         N, P, D, R = hip["N"], hip["P"], hip["D"], hip["R"]
-        if D > 8 or N - 1 > 64:
+        if D > MAX_DEPTH or N - 1 > MAX_ROWS:
             return None
-        W, V = IMAGE_HI - IMAGE_LO, self.vocab_size
-        nx = types.SimpleNamespace(C=C, L=_lib.lib(), dev=dev, N=N, P=P, D=D, R=R)
-        z = lambda *shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        nx.cand, nx.cart, nx.tcand = z(1, P, D, dt=torch.int64), z(1, P, D, dt=torch.float32), z(1, N, dt=torch.int64)
-        nx.win, nx.hot = z(N, W, dt=torch.float32), z(N, dt=torch.int32)
-        # the verdict record, double-buffered (the drafter keeps the previous step's bonus token / hidden rows while this step's are written):
-        # best, accept_len, counters[6], bonus token (int64 at words 8-9)
-        nx.recs = [z(16, dt=torch.int32), z(16, dt=torch.int32)]
-        nx.toks = [r_[8:10].view(torch.int64) for r_ in nx.recs]
-        nx.otok, nx.omass = z(1, dt=torch.int32), z(1, dt=torch.float32)
-        nx.out_hs, nx.acc = [None, None], z(1, D, dt=torch.int64)
-        nx.stream = torch.cuda.current_stream().cuda_stream          # (generate() runs on one stream)
-        nx.hid = None
-        nx.pos1 = (tb["tree_position_ids"].to(dev) + 1).to(torch.int64).contiguous()
-        nx.tree_indices, nx.retrieve = tb["tree_indices"].to(dev).contiguous(), tb["retrieve_indices"].to(dev).contiguous()
-        ri = nx.retrieve.clone()
-        ri[ri < 0] += N
-        nx.row_index = ri.to(torch.int32).contiguous()
-        n_sl = len(st.slabs)
-        L0 = st.input_ids.shape[1]
-        nx.lens = [(L0 - st.slab_off).to(dev).contiguous(), torch.zeros(n_sl, dtype=torch.int64, device=dev)]          # KV lengths: [this step, next step], swapped
-        nx.seq_len = [torch.full((1,), L0, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)]
-        nx.parity = 0
-        g = nx.group = (_lib.StepGroup * 1)()
-        a = g[0]
-        a.tree_indices, a.retrieve = nx.tree_indices.data_ptr(), nx.retrieve.data_ptr()
-        a.B, a.n_flat, a.N, a.P, a.D = 1, R * TOPK, N, P, D
-        a.tree_cand, a.cand, a.cart_prob = nx.tcand.data_ptr(), nx.cand.data_ptr(), nx.cart.data_ptr()
-        a.V, a.cfg, a.model = V, float(self.cfg_scale), ops.MODEL_LUMINA
-        a.pos_ids, a.pos_base = nx.pos1.data_ptr(), self.image_start_token_id_index + 3
-        a.w_latent, a.h_latent, a.img_lo, a.img_hi, a.newline_id, a.eos_id = self.w_latent_dim, self.h_latent_dim, IMAGE_LO, IMAGE_HI, 8803, 8196
+        V, L0 = self.vocab_size, st.input_ids.shape[1]
         top_k = self.internal_logits_processors[1].image_top_k if len(self.internal_logits_processors) > 1 else 0
-        a.top_k, a.win_lo, a.win_len, a.out_kind = min(top_k, V), IMAGE_LO, W, ops.ROWS_PROBS
-        a.out_win, a.row_hot, a.temperature, a.top_p = nx.win.data_ptr(), nx.hot.data_ptr(), 1.0, 1.0
-        cfg = self._ep_config(lantern, lantern_k, lantern_delta)
-        p = a.ep
-        p.B, p.P, p.D, p.V, p.rows_per_seq = 1, P, D, V, N
-        p.mode, p.syntax_shortcut, p.tok_offset = cfg.mode, int(cfg.syntax_shortcut), cfg.tok_offset
-        p.img_lo, p.img_hi, p.n_syntax = cfg.img_lo, min(cfg.img_hi, 2 ** 31 - 1), len(cfg.syntax)
-        for i, sx in enumerate(cfg.syntax):
-            p.syntax[i] = int(sx)
-        p.lantern, p.k, p.delta = int(cfg.lantern), int(cfg.k), float(cfg.delta)
-        p.top_k, p.temperature, p.top_p = 0, 1.0, 1.0
-        fifo = self._uniforms()
-        p.n_uniforms, p.R, p.N, p.row_index_per_seq = fifo.buf.shape[1], R, N, 0
-        nx.table = self._packed_table(int(lantern_k)) if lantern else None
-        if nx.table is not None:
-            p.table_rows, p.table_cols = nx.table.shape
-        b = a.ep_buf
-        b.logits, b.row_index, b.cand, b.cart_prob = nx.win.data_ptr(), nx.row_index.data_ptr(), nx.cand.data_ptr(), nx.cart.data_ptr()
-        b.op_off, b.p_idx, b.b_off, b.b_idx = hip["op_off"].data_ptr(), hip["p_idx"].data_ptr(), hip["b_off"].data_ptr(), hip["b_idx"].data_ptr()
-        b.tree_cand, b.nn_table = nx.tcand.data_ptr(), (nx.table.data_ptr() if nx.table is not None else None)
-        b.uniforms, b.cursor = fifo.buf.data_ptr(), fifo.cursor.data_ptr()
-        w = a.ep_win
-        w.win_lo, w.win_len, w.row_hot, w.rows_kind = IMAGE_LO, W, nx.hot.data_ptr(), ops.ROWS_PROBS
-        w.orig_prob_stride, w.orig_prob_offset = V, IMAGE_LO
-        w.out_tok, w.out_mass = nx.otok.data_ptr(), nx.omass.data_ptr()
         nodes = hip.get("nodes") if (self.ep_form == "nodes" and (not lantern or int(lantern_k) + 1 <= 1024)) else None
-        nx.nodes_struct = None
-        if nodes is not None:
-            nbytes = int(nx.L.lantern_evaluate_posterior_nodes_workspace(C.byref(p), C.byref(w), nodes.n_internal, 0))
-            nx.nodes_ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-            nx.nodes_struct = nodes.struct(nx.nodes_ws.data_ptr(), nbytes, -1)
-            a.nodes = C.pointer(nx.nodes_struct)
-        a.slab_ptrs, a.slab_seq = st.slab_ptrs.data_ptr(), st.slab_seq.data_ptr()
-        S, d = s0.shape[-2], s0.shape[-1]
-        a.n_slabs, a.elem_bytes, a.outer, a.S_max, a.d = n_sl, s0.element_size(), s0.numel() // (S * d), S, d
-        a.accepted_tokens = nx.acc.data_ptr()
-        a.hid_groups = 2
-        # ---- host work taken out of the step (round 5): the verdict where the host can poll it, a block of bonus uniforms, input_ids appended in place
-        nx.verdict = nx.verdict_np = None
-        try:
-            nx.verdict = torch.zeros(16, dtype=torch.int32).pin_memory()          # evaluate_posterior writes the record here as well (ep_win.verdict_host)
-            nx.verdict_np = nx.verdict.numpy()
-            w.verdict_host = nx.verdict.data_ptr()
-        except RuntimeError:
-            nx.verdict = nx.verdict_np = None
-        nx.ids_buf = None
-        if st.input_ids.device == dev and st.input_ids.dim() == 2:
-            cap = max(int(getattr(st, "max_length", 4096)), L0) + 2 * D + 64
-            nx.ids_buf = torch.zeros((1, cap), dtype=torch.int64, device=dev)
-            nx.ids_buf[:, :L0] = st.input_ids[:1]
-            a.ids_buf, a.ids_stride = nx.ids_buf.data_ptr(), cap
+        # host work taken out of the step (round 5): the verdict where the host can poll it, a block of bonus uniforms, input_ids appended in place
+        inplace_ids = st.input_ids.device == dev and st.input_ids.dim() == 2
+        nx = OneCallStep(st.slabs, st.slab_ptrs, st.slab_seq, N=N, P=P, D=D, R=R, V=V, win_lo=IMAGE_LO, win_len=IMAGE_HI - IMAGE_LO,
+                         ep_cfg=self._ep_config(lantern, lantern_k, lantern_delta), model=ops.MODEL_LUMINA, cfg_scale=self.cfg_scale,
+                         top_k=min(top_k, V), img_lo=IMAGE_LO, img_hi=IMAGE_HI,
+                         pos_ids=(tb["tree_position_ids"].to(dev) + 1).to(torch.int64).contiguous(), pos_base=self.image_start_token_id_index + 3,
+                         w_latent=self.w_latent_dim, h_latent=self.h_latent_dim, newline_id=8803, eos_id=8196,
+                         fifo=self._uniforms(), table=self._packed_table(int(lantern_k)) if lantern else None,
+                         tree=dict(hip, tree_indices=tb["tree_indices"], retrieve=tb["retrieve_indices"]), nodes=nodes, pinned_verdict=True,
+                         ids=st.input_ids[:1] if inplace_ids else None, ids_cap=max(int(getattr(st, "max_length", 4096)), L0) + 2 * D + 64)
+        # KV lengths: [this step, next step], swapped with the step's parity (the commit advances them on the device)
+        st.native_lens = [(L0 - st.slab_off).to(dev).contiguous(), torch.zeros(len(st.slabs), dtype=torch.int64, device=dev)]
         return nx
 
     _UB_BLOCK = 4096          # bonus-draw uniforms generated per torch.rand call (one per verify step before)
@@ -535,88 +444,24 @@ class EaLumina_mGPT(nn.Module):
         draw, the KV / hidden / token commit (only where the walk reported no status) -- on preallocated buffers, and one host read of the 40-byte
         verdict record.  Same kernels, same uniforms (`_bonus_uniform`: one block shared by every path), same results as the per-kernel path
         (tests/test_gpu_generate_ref.py runs both, with blocks of 1 and of 8 recorded uniforms)."""
-        C, L, a = nx.C, nx.L, nx.group[0]
         tl = st.tree_logits
-        dev = nx.dev
-        # (host time is what this path costs at a batch of one: no-op conversions are skipped, constant argument objects are built once)
-        ss_token = tl[0] if (tl[0].device == dev and tl[0].is_contiguous()) else tl[0].to(dev).contiguous()
-        ss_prob = tl[1] if (tl[1].device == dev and tl[1].dtype == torch.float32 and tl[1].is_contiguous()) else tl[1].to(dev).float().contiguous()
-        sample = st.sample_token
-        sample = sample.reshape(-1) if (sample.device == dev and sample.is_contiguous()) else sample.to(dev).reshape(-1)[:1].contiguous()
-        stream = nx.stream
-        par = nx.parity
-        rec, tokbuf = nx.recs[par], nx.toks[par]
-        pc = nx.__dict__.get("_per_parity")
-        if pc is None:
-            pc = nx._per_parity = [(r_.data_ptr(), t_.data_ptr()) for r_, t_ in zip(nx.recs, nx.toks)]
-            nx._gc_const = tuple(C.c_void_p(x) for x in (a.tree_indices, a.retrieve, a.tree_cand, a.cand, a.cart_prob, stream))
-        rp, tp = pc[par]
-        eb, ew = a.ep_buf, a.ep_win
-        eb.best, eb.accept_len, eb.counters = rp, rp + 4, rp + 8
-        ew.token = tp
-        p_tok, p_prob, p_smp = ss_token.data_ptr(), ss_prob.data_ptr(), sample.data_ptr()
-        a.stream, a.ss_token = stream, None          # (ss_token NULL: lantern_verify_step takes the candidates as this call leaves them -- no second O6 launch)
-        a.flags = ops._lib.STEP_CANDIDATES_READY
-        g = nx._gc_const
-        ops.check(L.lantern_gather_candidates(C.c_void_p(p_tok), C.c_void_p(p_prob), C.c_void_p(p_smp), g[0], g[1], 1, a.n_flat, nx.N, nx.P, nx.D, g[2], g[3], g[4], g[5]),
-                  "gather_candidates")
+        nx.begin()
+        nx.gather_candidates(tl[0], tl[1], st.sample_token)
         tree_logits, uncond_logits, hidden, uhidden, _pos = self._tree_forward(nx.tcand, st.attn_mask, self.past_key_values, st.tree_position_ids, st.input_ids)
-        cl, ul = tree_logits[0], uncond_logits[0]
-        if cl.dtype != ul.dtype or cl.dtype not in (torch.bfloat16, torch.float32):
-            cl, ul = cl.float(), ul.float()
-        if not cl.is_contiguous():
-            cl = cl.contiguous()
-        if not ul.is_contiguous():
-            ul = ul.contiguous()
-        a.cond, a.uncond, a.dtype = cl.data_ptr(), ul.data_ptr(), int(cl.dtype == torch.bfloat16)
-        # the drafter's distributions, level by level: one [R, V] f32 block (no copy when the levels already sit back to back)
-        ol = tl[2]
-        ptrs = [o.data_ptr() for o in ol]
-        if (all(o.dtype == torch.float32 and o.is_contiguous() and o.device == dev for o in ol) and
-                all(ptrs[i] + 4 * ol[i].numel() == ptrs[i + 1] for i in range(len(ol) - 1))):
-            orig = ol
-            eb.orig_prob = ptrs[0]
-        else:
-            orig = concat_original_prob(ol)
-            eb.orig_prob = orig.data_ptr()
-        h0, h1 = hidden[0], uhidden[0]
-        if h0.is_contiguous() and h1.is_contiguous() and h0.dtype == h1.dtype and h0.shape == h1.shape and h0.device == dev and h1.device == dev:
-            hid, a.hidden, a.hidden_uncond = h0, h0.data_ptr(), h1.data_ptr()          # the two passes' rows as two pointers: nothing is stacked
-        else:
-            hid = torch.stack((h0, h1))[None]                                              # [1, 2, N, H]
-            a.hidden, a.hidden_uncond = hid.data_ptr(), None
-        out_h = nx.out_hs[par]
-        if out_h is None or out_h.dtype != hid.dtype or out_h.shape[-1] != hid.shape[-1]:
-            out_h = nx.out_hs[par] = torch.zeros((1, 2, nx.D, hid.shape[-1]), dtype=hid.dtype, device=nx.dev)
-        a.out_hidden, a.hid_elem_bytes, a.H = out_h.data_ptr(), hid.element_size(), hid.shape[-1]
+        cl, ul = nx.bind_rows(tree_logits[0], uncond_logits[0])
+        nx.bind_orig_prob(tl[2])
+        out_h = nx.bind_hidden_pair(hidden[0], uhidden[0])
         fifo = self._uniforms()
         fifo.reserve(nx.N - 1)                                                             # one uniform per tried candidate, every non-root node at most once
-        u = self._bonus_uniform(dev)                                                       # the bonus draws' uniforms: one torch.rand per _UB_BLOCK steps
-        ew.u_bonus = u.data_ptr()
-        cur, nxt = nx.lens[par], nx.lens[par ^ 1]
-        a.slab_prev, a.new_len, a.seq_len = cur.data_ptr(), nxt.data_ptr(), cur.data_ptr()          # (slab 0 is a cond slab at offset 0: its length is len(input_ids))
+        u = self._bonus_uniform(nx.dev)                                                    # the bonus draws' uniforms: one torch.rand per _UB_BLOCK steps
+        nx.bind_bonus(u)
+        cur, nxt = st.native_lens[nx.parity], st.native_lens[nx.parity ^ 1]
+        nx.bind_lengths(cur, nxt, seq_len=cur)          # (slab 0 is a cond slab at offset 0: its length is len(input_ids))
         Lcur = st.input_ids.shape[1]
-        inplace_ids = nx.ids_buf is not None and Lcur + nx.D + 2 <= nx.ids_buf.shape[1]
-        a.ids_buf, a.ids_len = (nx.ids_buf.data_ptr() if inplace_ids else None), (cur.data_ptr() if inplace_ids else None)
-        vh = nx.verdict_np
-        if vh is not None:
-            vh[10] = 0
-        ops.check(L.lantern_verify_step(nx.group, 1), "verify_step")
-        # the step's one host read: the verdict record, polled in pinned memory where evaluate_posterior wrote it (visible as soon as the walk is
-        # done, while the commit still runs) -- no copy, no stream synchronisation; `rec.tolist()` when there is no pinned record
-        r = None
-        if vh is not None:
-            spins = 0
-            while vh[10] == 0:
-                spins += 1
-                if spins > 2_000_000:          # (seconds: something is badly wrong -- take the synchronising read)
-                    break
-            if vh[10] != 0:
-                r = vh[:10].tolist()
-                r[8] = (r[8] & 0xffffffff) | (r[9] << 32)
-        if r is None:
-            r = rec.tolist()
-        best, alen, n_used, status, tok = r[0], r[1], r[5], r[7], r[8]
+        inplace_ids = nx.bind_ids(Lcur, cur)
+        nx.launch()
+        best, alen, n_used, status, tok = nx.verdict()
+        nx.end()
         fifo.consumed(n_used)
         if status != 0:
             if status in self._RETRY_DENSE:
@@ -625,34 +470,32 @@ class EaLumina_mGPT(nn.Module):
                 fifo.cursor.sub_(n_used)
                 rows = WindowRows(nx.win, nx.hot, st.retrieve_indices, self.vocab_size, IMAGE_LO)
                 top_k = self.internal_logits_processors[1].image_top_k if len(self.internal_logits_processors) > 1 else 0
-                kw = dict(model=ops.MODEL_LUMINA, pos_ids=(nx.pos1 + Lcur).reshape(-1), pos_base=self.image_start_token_id_index + 3, w=self.w_latent_dim,
+                kw = dict(model=ops.MODEL_LUMINA, pos_ids=(nx.pos_ids + Lcur).reshape(-1), pos_base=self.image_start_token_id_index + 3, w=self.w_latent_dim,
                           h=self.h_latent_dim, img_lo=IMAGE_LO, img_hi=IMAGE_HI, newline_id=8803, eos_id=8196, top_k=min(top_k, self.vocab_size))
                 rows.dense_source = lambda: NodeLogits(ops.cfg_mask_topk(cl, ul, float(self.cfg_scale), **kw), st.retrieve_indices)
                 bc, al, sample_p = self.evaluate_posterior(rows.dense_rows(), nx.cand[0], nx.cart[0], tl[2], self.tree_buffers["p_indices"], nx.tcand,
                                                            self.tree_buffers["b_indices"], True, lantern, lantern_k, lantern_delta)
                 hit = self._commit_from_host(st, nx.cand[0], bc, al, hidden, uhidden, sample_p, u, None)
                 nxt.copy_(cur + (int(al) + 1))
-                nx.parity ^= 1
-                if nx.ids_buf is not None and st.input_ids.shape[1] <= nx.ids_buf.shape[1]:          # keep the in-place copy of input_ids in step
-                    nx.ids_buf[:, :st.input_ids.shape[1]] = st.input_ids[:1]
+                nx.resync_ids(st.input_ids)
                 return hit
-            ops.raise_on_status(rec[2:8].reshape(1, 6))
+            nx.raise_on_status()
         n = alen + 1
-        nx.parity ^= 1
         done = set()
         for clen, off in zip(self._length_tensors(st), st.offsets):          # (one length tensor per cache, shared by its slabs)
             if (id(clen), off) not in done:
                 clen.fill_(Lcur - off + n)
                 done.add((id(clen), off))
+        token = nx.token.reshape(1, 1)
         if inplace_ids:          # the commit appended the accepted tokens and, behind them, the bonus token: views, no torch.cat
             st.input_ids = nx.ids_buf[:, :Lcur + n]
-            self._draft_next(st, out_h[:, 0, :n], out_h[:, 1, :n], tokbuf.reshape(1, 1), ids_with_token=nx.ids_buf[:, :Lcur + n + 1])
+            self._draft_next(st, out_h[:, 0, :n], out_h[:, 1, :n], token, ids_with_token=nx.ids_buf[:, :Lcur + n + 1])
         else:
             accepted = nx.acc[:, :n]
             if accepted.device != st.input_ids.device:
                 accepted = accepted.to(st.input_ids.device)
             st.input_ids = torch.cat([st.input_ids[None, 0] if st.parallel else st.input_ids, accepted], dim=-1)
-            self._draft_next(st, out_h[:, 0, :n], out_h[:, 1, :n], tokbuf.reshape(1, 1))      # (views of this parity's buffers: the next step writes the other pair)
+            self._draft_next(st, out_h[:, 0, :n], out_h[:, 1, :n], token)      # (views of this parity's buffers: the next step writes the other pair)
         st.new_token += n
         st.accept_lengths.append(n)
         return False

@@ -260,6 +260,23 @@ class EpConfig:
         return EpConfig(mode=MODE_STATIC_LG if static else MODE_DYNAMIC, tok_offset=4, img_lo=4, img_hi=8196, **kw)
 
 
+def fill_ep_params(dst: EpParams, cfg: EpConfig, *, B: int, P: int, D: int, V: int, rows_per_seq: int, n_uniforms: int, top_k: int,
+                   temperature: float, top_p: float, R: int = 0, N: int = 0, row_index_per_seq: int = 0, table_shape=None) -> EpParams:
+    """`cfg` and a launch's shapes written into `dst` IN PLACE (lantern_step_group.ep is an embedded struct) -- the one place that transcribes an
+    EpConfig.  The processors are arguments, not read from `cfg`: rows that are already final probabilities take top_k=0, temperature=1, top_p=1."""
+    dst.B, dst.P, dst.D, dst.V, dst.rows_per_seq = B, P, D, V, rows_per_seq
+    dst.mode, dst.tok_offset, dst.syntax_shortcut = cfg.mode, cfg.tok_offset, int(cfg.syntax_shortcut)
+    dst.img_lo, dst.img_hi, dst.n_syntax = cfg.img_lo, min(cfg.img_hi, 2 ** 31 - 1), len(cfg.syntax)
+    for i, s in enumerate(cfg.syntax):
+        dst.syntax[i] = int(s)
+    dst.lantern, dst.k, dst.delta = int(cfg.lantern), int(cfg.k), float(cfg.delta)
+    dst.top_k, dst.temperature, dst.top_p = int(top_k), float(temperature), float(top_p)
+    dst.n_uniforms, dst.R, dst.N, dst.row_index_per_seq = n_uniforms, R, N, row_index_per_seq
+    if table_shape is not None:
+        dst.table_rows, dst.table_cols = table_shape
+    return dst
+
+
 @dataclass
 class StaticAux:
     cart_prob: torch.Tensor   # [B,P,D] f32
@@ -285,24 +302,16 @@ def evaluate_posterior(cfg: EpConfig, logits, row_index, cand, uniforms, table=N
     rows = logits.shape[-2]
     assert logits.shape[0] == B
     dev = logits.device
-    prm = EpParams()
-    prm.B, prm.P, prm.D, prm.V, prm.rows_per_seq = B, P, D, V, rows
-    prm.mode, prm.syntax_shortcut, prm.tok_offset = cfg.mode, int(cfg.syntax_shortcut), cfg.tok_offset
-    prm.img_lo, prm.img_hi = cfg.img_lo, min(cfg.img_hi, 2 ** 31 - 1)
-    prm.n_syntax = len(cfg.syntax)
-    for i, s in enumerate(cfg.syntax):
-        prm.syntax[i] = int(s)
-    prm.lantern, prm.k, prm.delta = int(cfg.lantern), int(cfg.k), float(cfg.delta)
-    prm.top_k, prm.temperature, prm.top_p = int(cfg.top_k), float(cfg.temperature), float(cfg.top_p)
-    prm.n_uniforms = uniforms.shape[1]
-    prm.row_index_per_seq = int(row_index.dim() == 3)
+    prm = fill_ep_params(EpParams(), cfg, B=B, P=P, D=D, V=V, rows_per_seq=rows, n_uniforms=uniforms.shape[1],
+                         top_k=cfg.top_k, temperature=cfg.temperature, top_p=cfg.top_p,
+                         R=aux.orig_prob.shape[1] if aux is not None else 0, N=aux.tree_cand.shape[1] if aux is not None else 0,
+                         row_index_per_seq=int(row_index.dim() == 3), table_shape=None if table is None else table.shape)
     buf = EpBuffers()
     if table is not None:
         if not table.is_cuda:
             raise _lib.LanternError("evaluate_posterior: table must be a device tensor")
         assert table.element_size() == 2
         table = table.contiguous()
-        prm.table_rows, prm.table_cols = table.shape
         buf.nn_table = table.data_ptr()
     keep = []
     if aux is not None:
@@ -312,8 +321,6 @@ def evaluate_posterior(cfg: EpConfig, logits, row_index, cand, uniforms, table=N
              _dev(aux.tree_cand, torch.int64, "tree_cand")]
         keep.extend(a)
         buf.cart_prob, buf.orig_prob, buf.op_off, buf.p_idx, buf.b_off, buf.b_idx, buf.tree_cand = [x.data_ptr() for x in a]
-        prm.R = a[1].shape[1]
-        prm.N = a[6].shape[1]
         ws = torch.empty((B, V), dtype=torch.float32, device=dev)
         keep.append(ws)
         buf.workspace = ws.data_ptr()
@@ -527,22 +534,14 @@ def evaluate_posterior_window(cfg: EpConfig, V: int, win_logits, win_lo: int, ro
     B, P, D = cand.shape
     rows, W = win_logits.shape[-2], win_logits.shape[-1]
     dev = win_logits.device
-    prm = EpParams()
-    prm.B, prm.P, prm.D, prm.V, prm.rows_per_seq = B, P, D, V, rows
-    prm.mode, prm.syntax_shortcut, prm.tok_offset = cfg.mode, int(cfg.syntax_shortcut), cfg.tok_offset
-    prm.img_lo, prm.img_hi = cfg.img_lo, min(cfg.img_hi, 2 ** 31 - 1)
-    prm.n_syntax = len(cfg.syntax)
-    for i, s in enumerate(cfg.syntax):
-        prm.syntax[i] = int(s)
-    prm.lantern, prm.k, prm.delta = int(cfg.lantern), int(cfg.k), float(cfg.delta)
-    prm.top_k, prm.temperature, prm.top_p = int(cfg.top_k), float(cfg.temperature), float(cfg.top_p)
-    prm.n_uniforms = uniforms.shape[1]
-    prm.row_index_per_seq = int(row_index.dim() == 3)
+    prm = fill_ep_params(EpParams(), cfg, B=B, P=P, D=D, V=V, rows_per_seq=rows, n_uniforms=uniforms.shape[1],
+                         top_k=cfg.top_k, temperature=cfg.temperature, top_p=cfg.top_p,
+                         R=aux.orig_prob.shape[1] if aux is not None else 0, N=aux.tree_cand.shape[1] if aux is not None else 0,
+                         row_index_per_seq=int(row_index.dim() == 3), table_shape=None if table is None else table.shape)
     buf, win = EpBuffers(), EpWindow()
     keep = []
     if table is not None:
         table = table.contiguous()
-        prm.table_rows, prm.table_cols = table.shape
         buf.nn_table = table.data_ptr()
     if aux is not None:
         a = [_dev(aux.cart_prob, torch.float32, "cart_prob"), _dev(aux.orig_prob, torch.float32, "orig_prob"),
@@ -550,7 +549,6 @@ def evaluate_posterior_window(cfg: EpConfig, V: int, win_logits, win_lo: int, ro
              _dev(aux.b_idx, torch.int32, "b_idx"), _dev(aux.tree_cand, torch.int64, "tree_cand")]
         keep.extend(a)
         buf.cart_prob, buf.orig_prob, buf.op_off, buf.p_idx, buf.b_off, buf.b_idx, buf.tree_cand = [x.data_ptr() for x in a]
-        prm.R, prm.N = a[1].shape[1], a[6].shape[1]
         win.orig_prob_stride = a[1].shape[-1]
         win.orig_prob_offset = 0 if orig_windowed else win_lo
     out = dict(best=torch.empty(B, dtype=torch.int32, device=dev), accept_len=torch.empty(B, dtype=torch.int32, device=dev),

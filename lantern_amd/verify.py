@@ -80,6 +80,30 @@ class UniformFifo:
             self._last = n_used
 
 
+class MirrorBase:
+    """What the mirror classes share besides the step: the staged uniforms, the packed neighbour table, the statuses that send a step to the
+    dense kernel.  Expects `nearest_latents`, `uniform_window` and `_fifo` on the class that mixes it in."""
+
+    # statuses of the windowed kernel the dense kernel does not have (the residual vanished, uniforms / tree beyond its LDS staging)
+    _RETRY_DENSE = (2, 6, 7, 8)
+
+    def _packed_table(self, k: int) -> torch.Tensor:
+        """Neighbour table in the hot-path layout (16-byte aligned rows of ceil8(k+1) ids, lantern_pack_vq_table), built once per k;
+        tables too narrow to pad (k + 1 > 1024 staged ids is the kernel's limit anyway) are passed through."""
+        cols = -(-(k + 1) // 8) * 8
+        if cols > min(1024, self.nearest_latents.shape[1]):
+            return self.nearest_latents
+        cache = self.__dict__.setdefault("_packed_tables", {})
+        if cols not in cache:
+            cache[cols] = ops.pack_vq_table(self.nearest_latents, cols)
+        return cache[cols]
+
+    def _uniforms(self) -> UniformFifo:
+        if self._fifo is None:
+            self._fifo = UniformFifo(self.nearest_latents.device, window=self.uniform_window)
+        return self._fifo
+
+
 class NodeLogits:
     """Processed tree-node logits `[N,V]` + `retrieve_indices [P,D]`: what the reference's
     `tree_decoding` returns as the gathered `[P,D,V]` tensor, without materialising it.
