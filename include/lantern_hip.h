@@ -659,6 +659,28 @@ int lantern_head_expand_streamk(const void *A, const void *W, const void *bias, 
                                 size_t sk_workspace_bytes, void *stream);
 size_t lantern_pack_linear_weight_bytes(int n_rows, int K, int pair_rows);
 int lantern_pack_linear_weight(const void *W, int n_rows, int K, int pair_rows, void *out, void *stream);
+/* FP8 weight streaming (weight-only, OCP e4m3fn, one f32 scale per output row) for the same kernels.  Every `packed` / `*_packed` argument above and
+ * below takes LANTERN_PACKED_BF16 (any non-zero value other than 2: the output of lantern_pack_linear_weight, as before) or LANTERN_PACKED_FP8 (the
+ * output of lantern_pack_linear_weight_fp8): lantern_linear_rows_streamk (epilogues 0, LANTERN_EPI_RESIDUAL, LANTERN_EPI_SILU_MUL),
+ * lantern_drafter_fc_streamk, lantern_head_expand_streamk, lantern_head_sample and fc_packed / layer_packed / head_packed of lantern_draft_depth.
+ *   s[n]    = max_k |W[n,k]| / 448 in f32 (1 for an all-zero row);   q[n,k] = e4m3fn_rne(f32(W[n,k]) / s[n]), saturating at +-448, never a NaN code
+ *   out[m,n] = bf16(sum_k A[m,k] * q[n,k] * s[n] + bias[n]) -- the codes are expanded to bf16 exactly (v_cvt_scalef32_pk_bf16_fp8), contracted by the
+ *   same bf16 MFMAs in the same order as the bf16 packed weight, and the finished f32 sum is multiplied by s[n] before the bias; the later roundings of
+ *   every epilogue are unchanged (a gate / up pair uses its two scales, the CFG epilogue scales both rows before its bf16 steps).  Activations stay bf16.
+ * The buffer holds the brick sequence of lantern_pack_linear_weight (one brick per 32-row tile, 64-element K block and set; gate / up interleaved per
+ * brick; n_rows padded to a multiple of 32 with zero rows) at one byte per element, then the f32 scales of all padded rows: ONE pointer, so no
+ * signature grows.  The byte order inside a brick is private to the library: read codes and scales back with lantern_unpack_linear_weight_fp8
+ * (q_out [N, K] uint8 row-major, scale_out [N] f32, N = n_rows or 2 * pair_rows as for the source weight).  lantern_pack_linear_weight_fp8 quantises
+ * and packs on the device (one pass for the row maxima, one for the bricks); W [dev] bf16 row-major, out [dev]
+ * lantern_pack_linear_weight_fp8_bytes(n_rows, K, pair_rows) bytes, 16-byte aligned.  A combination without a kernel -- LANTERN_PACKED_FP8 with
+ * K % 64 != 0 -- returns LANTERN_E_UNSUPPORTED with a message; the per-tile entry points (lantern_linear_rows, _epilogue, _splitk, _packed,
+ * lantern_drafter_fc, lantern_head_expand) have no `packed` argument and read bf16 only: nothing falls back silently. */
+#define LANTERN_PACKED_BF16 1
+#define LANTERN_PACKED_FP8 2
+size_t lantern_pack_linear_weight_fp8_bytes(int n_rows, int K, int pair_rows);
+int lantern_pack_linear_weight_fp8(const void *W, int n_rows, int K, int pair_rows, void *out, void *stream);
+int lantern_unpack_linear_weight_fp8(const void *packed, int n_rows, int K, int pair_rows, uint8_t *q_out /* [N, K] */, float *scale_out /* [N] */,
+                                     void *stream);
 int lantern_rmsnorm_rows(const void *x, const void *weight, int M, int H, float eps, void *out, void *stream);
 int lantern_qk_norm_rope(const void *qkv, int B, int T, int n_q_heads, int n_kv_heads, int head_dim, const void *q_weight, const void *q_bias,
                          const void *k_weight, const void *k_bias, int model_parallel, const void *cos_table, const void *sin_table,

@@ -14,6 +14,8 @@
 // epilogue.  C/D map: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
 #include "common.h"
 
+#include <type_traits>
+
 namespace lantern {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -32,6 +34,23 @@ __device__ __forceinline__ bf16x8_t load_frag_nt(const uint16_t *p) {
     typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
     const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(p));
     return __builtin_bit_cast(bf16x8_t, v);
+}
+
+// FP8 (OCP e4m3fn) weight fragments: 16 bytes = this lane's elements of two consecutive MFMA steps (lantern_pack_linear_weight_fp8)
+__device__ __forceinline__ uint4 load_w8(const uint8_t *p) { return *reinterpret_cast<const uint4 *>(p); }
+__device__ __forceinline__ uint4 load_w8_nt(const uint8_t *p) {
+    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+    const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(p));
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+// eight e4m3 bytes -> the bf16x8 B operand: v_cvt_scalef32_pk_bf16_fp8 turns two bytes into a packed bf16 pair (scale 1: every finite e4m3 value is
+// a bf16 value, the conversion is exact); the row's f32 scale is applied once, to the finished sum, in the epilogue
+__device__ __forceinline__ bf16x8_t fp8x8_to_bf16x8(uint2 v) {
+    typedef __bf16 bf16x2v_t __attribute__((ext_vector_type(2)));
+    const bf16x2v_t p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.x, 1.0f, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.x, 1.0f, true);
+    const bf16x2v_t p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.y, 1.0f, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.y, 1.0f, true);
+    return __builtin_bit_cast(bf16x8_t, make_uint4(__builtin_bit_cast(unsigned int, p0), __builtin_bit_cast(unsigned int, p1),
+                                                   __builtin_bit_cast(unsigned int, p2), __builtin_bit_cast(unsigned int, p3)));
 }
 
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
@@ -731,6 +750,10 @@ extern "C" int lantern_linear_rows_splitk(const void *A, const void *W, const vo
 //    (measured 3.3 TB/s at best, whatever the occupancy or the prefetch depth: the DRAM pages, not the latency, were the limit).
 // Epilogues as in linear_rows_kernel (EPI 0 bias, 1 + residual, 2 gate / up pair with silu * mul; torch's bf16 roundings).
 constexpr int SK_CHUNK = 256;
+#ifndef LANTERN_SK_FP8_NBUF
+#define LANTERN_SK_FP8_NBUF 4
+#endif
+constexpr int SK_FP8_NBUF = LANTERN_SK_FP8_NBUF;          // trips in flight per wave of the FP8 instances (a trip carries half the weight bytes of a bf16 trip)
 
 struct SkArgs {
     const uint16_t *A, *W, *bias, *aux;
@@ -753,8 +776,17 @@ struct SkArgs {
     float embed_scale, cfg;          // cfg: EPI 3 (rows [0, M/2) conditional, [M/2, M) unconditional -> uncond + cfg * (cond - uncond) in bf16 steps)
 };
 
-template <int EPI, bool PACKED, int NBUF, bool GATHER = false, bool WNT = false>
+// W8: the packed weight holds FP8 (e4m3fn) codes, one byte per element, in the same brick sequence (lantern_pack_linear_weight_fp8: per brick 2 KB,
+// [half j][lane][16 bytes] = the lane's elements of MFMA steps 2j and 2j + 1, so a wave's load instruction is still 1 KB contiguous), the f32 scale of every
+// padded row behind the bricks.  A trip expands its bytes to the same bf16x8 operands (exactly) and runs the same MFMAs in the same order; the epilogue
+// multiplies the finished f32 sum by the row's scale before the bias.  NBUF = 4 there (SK_FP8_NBUF): a trip carries half the weight bytes, so twice the
+// trips keep the bytes in flight per wave where the bf16 form has them -- measured, 2 / 3 / 4 trips are the same within 2 % (7B products 18.4 - 19.0 /
+// 26.4 - 26.7 / 15.4 - 16.0 us): the FP8 form is not limited by its bytes in flight (it reaches 2.7 - 3.4 TB/s of weights where bf16 reaches 4.4 - 4.8;
+// what was tried on that: EXPERIMENTS.md "FP8 weight streaming").
+template <int EPI, bool PACKED, int NBUF, bool GATHER = false, bool WNT = false, bool W8 = false>
 __global__ __launch_bounds__(FC_THREADS) void linear_rows_streamk_kernel(const SkArgs a) {
+    static_assert(!W8 || PACKED, "FP8 weights exist in the packed layout only");
+    using wreg_t = typename std::conditional<W8, uint2, bf16x8_t>::type;
     constexpr int NSET = EPI == 2 ? 2 : 1;
     __shared__ float red[NSET][FC_WAVES][32][33];
     __shared__ uint32_t s_last;
@@ -783,6 +815,8 @@ __global__ __launch_bounds__(FC_THREADS) void linear_rows_streamk_kernel(const S
         erow = a.embed + (size_t)id * a.hsplit;
     }
     const bf16x8_t zero = __builtin_bit_cast(bf16x8_t, make_uint4(0, 0, 0, 0));
+    // W8: scale of padded row n of set s at wscale[s * 32 n_tiles + n], behind the brick stream
+    const float *wscale = W8 ? reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(a.W) + (size_t)a.n_tiles * 32 * K * NSET) : nullptr;
     // 8 consecutive k of this lane's activation row (GATHER: the embedding row, scaled and re-rounded to bf16 as
     // cnets_lumina_mgpt.py:1096-1097 does, for k < hsplit, the hidden row behind it; hsplit % 64 == 0: a trip never straddles the seam)
     auto a_frag = [&](int k0) -> bf16x8_t {
@@ -829,10 +863,21 @@ __global__ __launch_bounds__(FC_THREADS) void linear_rows_streamk_kernel(const S
             for (int i = 0; i < 16; ++i) acc[s_][i] = 0.0f;
         // ---- the K range of this wave, four MFMA steps (64 elements, 64 contiguous bytes per lane and row) per trip, NBUF trips in flight
         // (a ring of register buffers with compile-time indices: a buffer is refilled as soon as its MFMAs have read it)
-        bf16x8_t wb[NBUF][NSET][4], ab[NBUF][4];
-        auto load_trip = [&](int ks, bf16x8_t (&wv)[NSET][4], bf16x8_t (&av)[4]) {
+        wreg_t wb[NBUF][NSET][4];
+        bf16x8_t ab[NBUF][4];
+        auto load_trip = [&](int ks, wreg_t (&wv)[NSET][4], bf16x8_t (&av)[4]) {
             const int kb = ks * 16 + 32 * h;
-            if constexpr (PACKED) {          // brick (tile t, K block ks / 4, set): [q][lane][8]
+            if constexpr (W8) {          // brick (tile t, K block ks / 4, set): [j][lane][16 bytes]
+                const uint8_t *brick = reinterpret_cast<const uint8_t *>(a.W) + ((size_t)((long long)t * (K / 64) + (ks >> 2)) * NSET) * 2048 + lane * 16;
+#pragma unroll
+                for (int s_ = 0; s_ < NSET; ++s_)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const uint4 v = WNT ? load_w8_nt(brick + s_ * 2048 + j * 1024) : load_w8(brick + s_ * 2048 + j * 1024);
+                        wv[s_][2 * j] = make_uint2(v.x, v.y);
+                        wv[s_][2 * j + 1] = make_uint2(v.z, v.w);
+                    }
+            } else if constexpr (PACKED) {          // brick (tile t, K block ks / 4, set): [q][lane][8]
                 const uint16_t *brick = a.W + ((size_t)((long long)t * (K / 64) + (ks >> 2)) * NSET) * 2048 + lane * 8;
 #pragma unroll
                 for (int s_ = 0; s_ < NSET; ++s_)
@@ -849,11 +894,16 @@ __global__ __launch_bounds__(FC_THREADS) void linear_rows_streamk_kernel(const S
 #pragma unroll
             for (int q = 0; q < 4; ++q) av[q] = a_frag(kb + 8 * q);
         };
-        auto mfma_trip = [&](const bf16x8_t (&wv)[NSET][4], const bf16x8_t (&av)[4]) {
+        auto mfma_trip = [&](const wreg_t (&wv)[NSET][4], const bf16x8_t (&av)[4]) {
 #pragma unroll
             for (int s_ = 0; s_ < NSET; ++s_)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) acc[s_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[q], wv[s_][q], acc[s_], 0, 0, 0);
+                for (int q = 0; q < 4; ++q) {
+                    bf16x8_t wq;
+                    if constexpr (W8) wq = fp8x8_to_bf16x8(wv[s_][q]);
+                    else wq = wv[s_][q];
+                    acc[s_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[q], wq, acc[s_], 0, 0, 0);
+                }
         };
         int ks = ks0;
 #pragma unroll
@@ -950,7 +1000,12 @@ __global__ __launch_bounds__(FC_THREADS) void linear_rows_streamk_kernel(const S
                     const int i = e >> 5, col = e & 31, n = t * 32 + col;
                     if (n < a.n_rows) {
                         const float b = a.bias ? bf16_bits_to_f32(a.bias[a.row_lo + n]) : 0.0f;
-                        const float c = bf16_bits_to_f32(f32_to_bf16_rne(red[0][0][i][col] + b)), u = bf16_bits_to_f32(f32_to_bf16_rne(red[0][0][i + n_half][col] + b));
+                        float sc = red[0][0][i][col], su = red[0][0][i + n_half][col];
+                        if constexpr (W8) {
+                            sc *= wscale[n];
+                            su *= wscale[n];
+                        }
+                        const float c = bf16_bits_to_f32(f32_to_bf16_rne(sc + b)), u = bf16_bits_to_f32(f32_to_bf16_rne(su + b));
                         const float o = round_bf16(u + round_bf16(a.cfg * round_bf16(c - u)));
                         a.out[(size_t)i * a.out_stride + a.out_col0 + n] = (uint16_t)(__float_as_uint(o) >> 16);
                     }
@@ -962,11 +1017,13 @@ __global__ __launch_bounds__(FC_THREADS) void linear_rows_streamk_kernel(const S
                 const int e = tid + j * FC_THREADS, m = e >> 5, n = t * 32 + (e & 31);
                 if (m < a.M && n < a.n_rows) {
                     float x = v[0][j];
+                    if constexpr (W8) x *= wscale[n];
                     if (a.bias) x += bf16_bits_to_f32(a.bias[a.row_lo + n]);
                     uint16_t o = f32_to_bf16_rne(x);
                     if constexpr (EPI == 1) o = f32_to_bf16_rne(bf16_bits_to_f32(a.aux[(size_t)m * a.aux_stride + n]) + bf16_bits_to_f32(o));
                     if constexpr (EPI == 2) {
                         float u = v[NSET - 1][j];
+                        if constexpr (W8) u *= wscale[a.n_tiles * 32 + n];
                         if (a.bias) u += bf16_bits_to_f32(a.bias[a.row_lo + a.pair_rows + n]);
                         const float gb = bf16_bits_to_f32(o), ub = bf16_bits_to_f32(f32_to_bf16_rne(u));
                         const float sg = bf16_bits_to_f32(f32_to_bf16_rne(gb / (1.0f + expf(-gb))));
@@ -1310,9 +1367,14 @@ extern "C" int lantern_pack_linear_weight(const void *W, int n_rows, int K, int 
 }
 
 // shared launch: shares of the (tile, K chunk) space over G workgroups, fixed workspace layout (partials, then counters)
-static int sk_run(SkArgs a, int epilogue, bool packed, bool gather, void *workspace, size_t workspace_bytes, hipStream_t st, const char *who) {
+static int sk_run(SkArgs a, int epilogue, int packed, bool gather, void *workspace, size_t workspace_bytes, hipStream_t st, const char *who) {
     LANTERN_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= lantern_linear_rows_streamk_workspace(a.n_rows),
                       "%s: workspace of lantern_linear_rows_streamk_workspace(n_rows) bytes, 16-byte aligned, zero-filled once", who);
+    const bool fp8 = packed == LANTERN_PACKED_FP8;
+    if (fp8 && a.K % 64 != 0) {
+        set_error("%s: an FP8 packed weight needs K %% 64 == 0 (K=%d): there is no kernel for this shape", who, a.K);
+        return LANTERN_E_UNSUPPORTED;
+    }
     if (packed) LANTERN_CHECK_ARG(a.K % 64 == 0, "%s: a packed weight needs K %% 64 == 0 (K=%d)", who, a.K);
     a.n_tiles = (a.n_rows + 31) / 32;
     a.cpt = (a.K + SK_CHUNK - 1) / SK_CHUNK;
@@ -1325,8 +1387,14 @@ static int sk_run(SkArgs a, int epilogue, bool packed, bool gather, void *worksp
     // count that fits the grid: no partial tiles at all) even where that leaves CUs idle (LlamaGen EAGLE-2 cycle 848 - 863 -> 822 - 831 us; 50 MB: slower).  lantern_tuning_set("sk_whole_mb", ..): the
     // size limit in MB (default 40: the 7B drafter's o_proj, 34 MB in 128 tiles, is still better off on 128 workgroups without partial tiles -- Lumina static
     // cycle 884 - 889 -> 865 - 868 us; 70, which takes in the 67 MB input stage: 878; 0 = never).
+    // The whole-tile rule goes by the SHAPE (its size as bf16), whatever the element format: it is a rule about tile counts and partial-tile round trips, and
+    // an FP8 weight must be cut exactly like the bf16 weight of the same shape -- same workgroup -> (tile, K range) assignment, same order of the f32 sums
+    // (measured the other way round, by fp8's real bytes: the 7B input stage, 128 tiles, fell onto 128 workgroups and went from 18.0 to 19.6 us).  The
+    // non-temporal rule below goes by the bytes the launch really streams (EXPERIMENTS.md "FP8 weight streaming").
+    const long long w_bytes_bf16 = (long long)a.n_tiles * 32 * a.K * 2 * (epilogue == LANTERN_EPI_SILU_MUL ? 2 : 1);
+    const long long w_bytes = fp8 ? w_bytes_bf16 / 2 : w_bytes_bf16;
     const int whole_mb = tuning(TUNE_SK_WHOLE_MB);
-    if (whole_mb > 0 && (long long)a.n_tiles * 32 * a.K * 2 * (epilogue == LANTERN_EPI_SILU_MUL ? 2 : 1) <= (long long)whole_mb * 1000000) {
+    if (whole_mb > 0 && w_bytes_bf16 <= (long long)whole_mb * 1000000) {
         int best = 1;
         for (int g = 1; g <= G && g <= a.n_tiles; ++g)
             if (a.n_tiles % g == 0) best = g;
@@ -1344,12 +1412,14 @@ static int sk_run(SkArgs a, int epilogue, bool packed, bool gather, void *worksp
     // drafter (tools/draft_bench.py lumina_static): threshold 200 MB (none) 1001 us per cycle, 120 (gate / up) 981, 95 (+ q/k/v) 931, 80 (+ down) 887-900,
     // 30 (all but o_proj) 901, 0 (all) 912.  lantern_tuning_set("sk_nt_min_mb", ..): negative = never.
     const int nt_min_mb = tuning(TUNE_SK_NT_MIN_MB);
-    a.w_stream = nt_min_mb >= 0 && (long long)a.n_tiles * 32 * a.K * 2 * (epilogue == LANTERN_EPI_SILU_MUL ? 2 : 1) >= (long long)nt_min_mb * 1000000 ? 1 : 0;
+    a.w_stream = nt_min_mb >= 0 && w_bytes >= (long long)nt_min_mb * 1000000 ? 1 : 0;
     // two trips in flight per wave: three and four measured the same (24.4 - 24.6 / 21.5 - 21.9 us for the 100 / 90 MB matrices) -- the kernel is
     // at the read bandwidth the part delivers (4.1 - 4.6 TB/s; torch's read-only reductions reach 3.8 - 4.0, its copy 5.2 read + write)
 #define SK_LAUNCH(E_, GA_)                                                                                                   \
     do {                                                                                                                  \
-        if (packed && a.w_stream) LANTERN_LAUNCH((linear_rows_streamk_kernel<E_, true, 2, GA_, true>), dim3(G), dim3(FC_THREADS), 0, st, a);   \
+        if (fp8 && a.w_stream) LANTERN_LAUNCH((linear_rows_streamk_kernel<E_, true, SK_FP8_NBUF, GA_, true, true>), dim3(G), dim3(FC_THREADS), 0, st, a);   \
+        else if (fp8) LANTERN_LAUNCH((linear_rows_streamk_kernel<E_, true, SK_FP8_NBUF, GA_, false, true>), dim3(G), dim3(FC_THREADS), 0, st, a);   \
+        else if (packed && a.w_stream) LANTERN_LAUNCH((linear_rows_streamk_kernel<E_, true, 2, GA_, true>), dim3(G), dim3(FC_THREADS), 0, st, a);   \
         else if (packed) LANTERN_LAUNCH((linear_rows_streamk_kernel<E_, true, 2, GA_>), dim3(G), dim3(FC_THREADS), 0, st, a);   \
         else LANTERN_LAUNCH((linear_rows_streamk_kernel<E_, false, 2, GA_>), dim3(G), dim3(FC_THREADS), 0, st, a);         \
     } while (0)
@@ -1378,7 +1448,7 @@ extern "C" int lantern_linear_rows_streamk(const void *A, const void *W, const v
     a.A = (const uint16_t *)A; a.W = (const uint16_t *)W; a.bias = (const uint16_t *)bias; a.aux = (const uint16_t *)aux; a.out = (uint16_t *)out;
     a.M = M; a.K = K; a.row_lo = row_lo; a.n_rows = n_rows; a.out_stride = out_stride; a.out_col0 = out_col0; a.aux_stride = aux_stride;
     a.pair_rows = epilogue == LANTERN_EPI_SILU_MUL ? pair_rows : 0;
-    return sk_run(a, epilogue, packed != 0, false, workspace, workspace_bytes, (hipStream_t)stream, "linear_rows_streamk");
+    return sk_run(a, epilogue, packed, false, workspace, workspace_bytes, (hipStream_t)stream, "linear_rows_streamk");
 }
 
 // O11 in stream-K form (M <= 32 rows: the drafting shape): the embedding gather, its scaling and the concat stay folded into the A-fragment
@@ -1392,7 +1462,7 @@ extern "C" int lantern_drafter_fc_streamk(const int64_t *ids, const void *hidden
     a.A = (const uint16_t *)hidden; a.W = (const uint16_t *)W; a.bias = (const uint16_t *)bias; a.out = (uint16_t *)out;
     a.M = M; a.K = 2 * H; a.n_rows = H; a.out_stride = H;
     a.ids = ids; a.embed = (const uint16_t *)embed; a.vocab = vocab; a.hsplit = H; a.embed_scale = embed_scale;
-    return sk_run(a, 0, packed != 0, true, workspace, workspace_bytes, (hipStream_t)stream, "drafter_fc_streamk");
+    return sk_run(a, 0, packed, true, workspace, workspace_bytes, (hipStream_t)stream, "drafter_fc_streamk");
 }
 
 namespace lantern {
@@ -1408,7 +1478,7 @@ int launch_drafter_fc_streamk_tables(const int64_t *ids, int n_flat, const int32
     a.M = M; a.K = 2 * H; a.n_rows = H; a.out_stride = H;
     a.ids = ids; a.embed = (const uint16_t *)embed; a.vocab = vocab; a.hsplit = H; a.embed_scale = embed_scale;
     a.in_gather = in_gather; a.in_rep = in_rep; a.rows_per_b = rows_per_b; a.src_T = src_T; a.n_flat = n_flat;
-    return sk_run(a, 0, packed != 0, true, workspace, workspace_bytes, st, "drafter_fc_streamk");
+    return sk_run(a, 0, packed, true, workspace, workspace_bytes, st, "drafter_fc_streamk");
 }
 }  // namespace lantern
 
@@ -1420,7 +1490,7 @@ int launch_linear_rows_cfg_streamk(const void *A, const void *W, const void *bia
     SkArgs a{};
     a.A = (const uint16_t *)A; a.W = (const uint16_t *)W; a.bias = (const uint16_t *)bias; a.out = (uint16_t *)win;
     a.M = 2 * n; a.K = K; a.row_lo = row_lo; a.n_rows = n_cols; a.out_stride = n_cols; a.cfg = cfg;
-    return sk_run(a, 3, packed != 0, false, workspace, workspace_bytes, st, "head_expand");
+    return sk_run(a, 3, packed, false, workspace, workspace_bytes, st, "head_expand");
 }
 }  // namespace lantern
 
@@ -1524,7 +1594,7 @@ int launch_linear_rows_streamk_seg(const void *A, int a_seg_rows, long long a_se
     a.M = M; a.K = K; a.n_rows = n_rows; a.out_stride = n_rows; a.aux_stride = aux_stride;
     a.pair_rows = epilogue == LANTERN_EPI_SILU_MUL ? pair_rows : 0;
     a.a_seg_rows = a_seg_rows; a.a_seg_stride = a_seg_stride;
-    return sk_run(a, epilogue, packed != 0, false, workspace, workspace_bytes, st, "linear_rows_streamk");
+    return sk_run(a, epilogue, packed, false, workspace, workspace_bytes, st, "linear_rows_streamk");
 }
 }  // namespace lantern
 

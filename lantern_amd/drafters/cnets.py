@@ -145,7 +145,7 @@ class DraftPlan:
             return t.data_ptr()
         emb = model.embed_tokens.weight
         a.embed = ptr(emb if emb.dtype == bf else emb.to(bf))
-        a.fc_w, a.fc_b, a.fc_packed = ptr(model._packed_weight("fc", model.fc.weight).data), ptr(model.fc.bias), 1
+        a.fc_w, a.fc_b, a.fc_packed = ptr(model._packed_weight("fc", model.fc.weight).data), ptr(model.fc.bias), model._packed_weight("fc", model.fc.weight).code
         if hasattr(layer, "input_layernorm"):
             a.ln1_w, a.eps1 = ptr(layer.input_layernorm.weight), float(layer.input_layernorm.variance_epsilon)
         wq, b = layer._packed_fused("qkv", (at.q_proj, at.k_proj, at.v_proj))
@@ -154,7 +154,7 @@ class DraftPlan:
         a.ln2_w = ptr(layer.post_attention_layernorm.weight)
         wg, bg = layer._packed_fused("gate_up", (mlp.gate_proj, mlp.up_proj), inter)
         a.gate_up_w, a.gate_up_b = ptr(wg.data), ptr(bg)
-        a.down_w, a.down_b, a.layer_packed = ptr(layer._packed("down", mlp.down_proj.weight).data), ptr(mlp.down_proj.bias), 1
+        a.down_w, a.down_b, a.layer_packed = ptr(layer._packed("down", mlp.down_proj.weight).data), ptr(mlp.down_proj.bias), wq.code          # (one format per layer: LANTERN_PACKED_*)
         if self.llama:
             self.freqs = model.freqs_cis.to(device=dev, dtype=torch.float32).contiguous()
             a.freqs, a.table_rows = ptr(self.freqs), self.freqs.shape[0]
@@ -163,7 +163,7 @@ class DraftPlan:
             a.qn_w, a.qn_b, a.kn_w, a.kn_b = ptr(at.q_norm.weight), ptr(at.q_norm.bias), ptr(at.k_norm.weight), ptr(at.k_norm.bias)
             a.model_parallel, a.cos_table, a.sin_table, a.table_rows = at.q_norm.weight.shape[0], ptr(cos), ptr(sin), cos.shape[0]
         # head
-        a.head_w, a.head_b, a.head_packed = ptr(hx["packed"].data if hx["packed"] is not None else head.weight), ptr(head.bias), int(hx["packed"] is not None)
+        a.head_w, a.head_b, a.head_packed = ptr(hx["packed"].data if hx["packed"] is not None else head.weight), ptr(head.bias), ops._packed_code(hx["packed"])
         a.row_lo, a.n_cols, a.model, a.cfg = hx["row_lo"], hx["n_cols"], hx["model"], float(model.cfg_scale)
         a.pos_base, a.w_latent, a.h_latent, a.newline_id, a.eos_id = 2, 48, 48, 8803, 8196
         a.top_k_filter, a.top_k = hx["top_k_filter"], k
@@ -547,14 +547,39 @@ class Model(nn.Module):
             return None
         return ops.drafter_attention_mask(attention_mask, tm, B, T, past_key_values_length, device=inputs_embeds.device)
 
+    weight_format = "bf16"          # set_weight_format("fp8"): the drafter's stream-K GEMMs read e4m3fn codes + a per-row scale (half the bytes per pass)
+
+    def set_weight_format(self, fmt: str):
+        """The element format of the packed weights this drafter streams at its drafting shape: its layers' four GEMMs, `fc`, and the head window.
+        "bf16" (default) or "fp8" (weight-only e4m3fn with one f32 scale per output row, ops.pack_linear_weight(fmt="fp8"); activations, accumulation
+        and every epilogue rounding as before).  The packed copies are dropped and re-made on the next call; the nn.Linear weights stay bf16.  A quantised
+        drafter changes what is PROPOSED, hence the accept length -- never the distribution of what is accepted (the accept test reads the drafter's own q)."""
+        from .decoder_layer import DecoderLayer
+        if fmt not in ("bf16", "fp8"):
+            raise ValueError(f"weight_format {fmt!r}: bf16 or fp8")
+        if fmt == "fp8":
+            w = self.fc.weight
+            if not (w.is_cuda and w.dtype == torch.bfloat16 and w.shape[0] % 64 == 0):
+                raise ops._lib.LanternError("set_weight_format('fp8'): needs bf16 weights on the device and hidden % 64 == 0 (the fp8 kernels read 64-element K blocks)")
+            if not all(isinstance(l, DecoderLayer) for l in self.layers):
+                raise ops._lib.LanternError("set_weight_format('fp8'): only this package's DecoderLayer / LlamaDecoderLayer read fp8 weights (injected layers do not)")
+        self.weight_format = fmt
+        for l in self.layers:
+            if isinstance(l, DecoderLayer):
+                l.weight_format = fmt
+        for name in ("_packed_weights", "_plan", "_splan"):
+            self.__dict__.pop(name, None)
+        return self
+
     def _packed_weight(self, name, weight, row_lo=0, n_rows=None):
-        """ops.pack_linear_weight of weight[row_lo : row_lo + n_rows], made once per weight version (the brick layout the stream-K kernel streams)."""
+        """ops.pack_linear_weight of weight[row_lo : row_lo + n_rows] in this model's weight_format, made once per weight version (the brick layout the
+        stream-K kernel streams)."""
         cache = self.__dict__.setdefault("_packed_weights", {})
-        key = (weight.data_ptr(), weight._version, row_lo, n_rows)
+        key = (weight.data_ptr(), weight._version, row_lo, n_rows, self.weight_format)
         hit = cache.get(name)
         if hit is None or hit[0] != key:
             rows = weight if n_rows is None else weight[row_lo:row_lo + n_rows]
-            hit = cache[name] = (key, ops.pack_linear_weight(rows.contiguous()))
+            hit = cache[name] = (key, ops.pack_linear_weight(rows.contiguous(), fmt=self.weight_format))
         return hit[1]
 
     def _input_stage(self, hidden_states, input_ids):
@@ -566,7 +591,8 @@ class Model(nn.Module):
             emb = emb if emb.dtype == torch.bfloat16 else emb.to(torch.bfloat16)
             ids, hid = input_ids.reshape(-1), hidden_states.reshape(B * T, H)
             out = torch.empty_like(hid)
-            pk = self._packed_weight("fc", w) if (B * T <= 32 and H % 64 == 0) else None          # the drafting shape streams the packed weight
+            fp8 = self.weight_format == "fp8"          # (fp8: every row count on the packed weight, prefills in 32-row blocks -- ops.drafter_fc)
+            pk = self._packed_weight("fc", w) if ((B * T <= 32 or fp8) and H % 64 == 0) else None          # the drafting shape streams the packed weight
             for s in range(0, B * T, 128):                     # one drafter call is <= ~120 rows; prefills go in slices
                 out[s:s + 128] = ops.drafter_fc(ids[s:s + 128], hid[s:s + 128], emb, w, self.fc.bias,
                                                 embed_scale=float(self.embed_upscale) if self.embed_upscale > 1.0 else 1.0, packed=pk)
@@ -780,7 +806,7 @@ class Model(nn.Module):
             return None
         # every tensor the plan snapshots a pointer (or a packed / converted copy) of: an in-place update of any of them -- or a new storage -- rebuilds it
         snap = [head.weight, head.bias, w, self.fc.bias, self.embed_tokens.weight] + [p_ for p_ in layer.parameters()]
-        key = (id(head), k, self.depth, hx["top_k_filter"], hx["model"]) + tuple((t.data_ptr(), t._version) for t in snap if t is not None)
+        key = (id(head), k, self.depth, hx["top_k_filter"], hx["model"], self.weight_format) + tuple((t.data_ptr(), t._version) for t in snap if t is not None)
         hit = self.__dict__.get("_plan")
         if hit is None or hit[0] != key:
             hit = self.__dict__["_plan"] = (key, DraftPlan(self, head, k, hx))
@@ -803,7 +829,7 @@ class Model(nn.Module):
         if hx is None or hx["packed"] is None:
             return None
         snap = [head.weight, head.bias, w, self.fc.bias, self.embed_tokens.weight] + [p_ for p_ in layer.parameters()]
-        key = (id(head), k, id(tb), hx["top_k_filter"], hx["model"]) + tuple((t.data_ptr(), t._version) for t in snap if t is not None)
+        key = (id(head), k, id(tb), hx["top_k_filter"], hx["model"], self.weight_format) + tuple((t.data_ptr(), t._version) for t in snap if t is not None)
         hit = self.__dict__.get("_splan")
         if hit is None or hit[0] != key:
             hit = self.__dict__["_splan"] = (key, StaticDraftPlan(self, head, k, hx, tb))

@@ -293,16 +293,33 @@ class DecoderLayer(nn.Module):
         self.input_layernorm = RMSNorm(config.hidden_size, eps)
         self.post_attention_layernorm = RMSNorm(config.hidden_size, eps)
 
+    @property
+    def weight_format(self) -> str:
+        """"bf16" (default) or "fp8": the element format of the packed weights the layer's four stream-K GEMMs read (ops.pack_linear_weight(fmt=..):
+        e4m3fn codes with a per-row f32 scale halve the bytes a drafting pass streams; the nn.Linear weights stay bf16).  Setting it drops the packed copies."""
+        return self.__dict__.get("_weight_format", "bf16")
+
+    @weight_format.setter
+    def weight_format(self, fmt: str):
+        if fmt not in ("bf16", "fp8"):
+            raise ValueError(f"weight_format {fmt!r}: bf16 or fp8")
+        if fmt != self.weight_format:
+            self.__dict__["_weight_format"] = fmt
+            self.__dict__.pop("_packed_weights", None)
+
     def _packed(self, name, weight, pair_rows=0):
         """The weight in the layout the stream-K kernel streams (ops.pack_linear_weight), made once per weight version; weights whose K is
-        not a multiple of 64 stay row-major (the kernel takes both)."""
+        not a multiple of 64 stay row-major (the kernel takes both) -- bf16 only: there is no fp8 kernel for them, and no silent change of format."""
+        fmt = self.weight_format
         if weight.shape[1] % 64:
+            if fmt != "bf16":
+                raise ops._lib.LanternError(f"weight_format = {fmt!r}: weight {name} has K = {weight.shape[1]} (K % 64 != 0), which only the bf16 kernels take")
             return weight
         cache = self.__dict__.setdefault("_packed_weights", {})
-        key = (weight.data_ptr(), weight._version)
+        key = (weight.data_ptr(), weight._version, fmt)
         hit = cache.get(name)
         if hit is None or hit[0] != key:
-            hit = cache[name] = (key, ops.pack_linear_weight(weight, pair_rows))
+            hit = cache[name] = (key, ops.pack_linear_weight(weight, pair_rows, fmt=fmt))
         return hit[1]
 
     def _packed_fused(self, name, mods, pair_rows=0):
@@ -310,16 +327,19 @@ class DecoderLayer(nn.Module):
         concatenation dropped again (the layer keeps the nn.Linear weights and the packed bricks, not a third copy: 280 MB at 7B size).  Keyed by the
         source weights' (data_ptr, version): load_state_dict and in-place optimiser steps re-pack; `repack()` after a write through `.data`."""
         ws = tuple(m.weight for m in mods)
+        fmt = self.weight_format
         if ws[0].shape[1] % 64:
+            if fmt != "bf16":
+                raise ops._lib.LanternError(f"weight_format = {fmt!r}: weight {name} has K = {ws[0].shape[1]} (K % 64 != 0), which only the bf16 kernels take")
             cat = torch.cat(ws, dim=0).contiguous()
             return cat, (None if mods[0].bias is None else torch.cat([m.bias for m in mods]).contiguous())
         cache = self.__dict__.setdefault("_packed_weights", {})
-        key = tuple((w.data_ptr(), w._version) for w in ws) + tuple((m.bias.data_ptr(), m.bias._version) for m in mods if m.bias is not None)
+        key = tuple((w.data_ptr(), w._version) for w in ws) + tuple((m.bias.data_ptr(), m.bias._version) for m in mods if m.bias is not None) + (fmt,)
         hit = cache.get(name)
         if hit is None or hit[0] != key:
             cat = torch.cat(ws, dim=0).contiguous()
             b = None if mods[0].bias is None else torch.cat([m.bias for m in mods]).contiguous()
-            hit = cache[name] = (key, ops.pack_linear_weight(cat, pair_rows), b)
+            hit = cache[name] = (key, ops.pack_linear_weight(cat, pair_rows, fmt=fmt), b)
             del cat
         return hit[1], hit[2]
 
@@ -417,6 +437,12 @@ class DecoderLayer(nn.Module):
             s[1][:, :, :past[1].shape[2]].copy_(past[1])
         return s
 
+    def _no_quiet_bf16(self):
+        """The torch composition reads the bf16 nn.Linear weights: a layer switched to another weight format must not slide onto it unnoticed."""
+        if self.fused and self.weight_format != "bf16":
+            raise ops._lib.LanternError(f"weight_format = {self.weight_format!r} exists on the fused HIP path only, and this call does not fit it (shape, dtype, "
+                                        "mask or position arguments); set `layer.fused = False` for the bf16 torch composition")
+
     fused = True          # False: every projection its own launch through skinny_linear / torch (the composition the fast path is tested against)
 
     supports_tree_bits = True      # Model.forward hands the tree block over as ancestor words (tree_bits / tree_keys / kv_start) when it has one
@@ -438,6 +464,7 @@ class DecoderLayer(nn.Module):
             y, present = self._fast(hidden_states, attention_mask, position_ids, past_key_value, use_cache, tree_bits, tree_keys, kv_start,
                                     causal and tree_bits is None)
             return (y, present) if use_cache else (y,)
+        self._no_quiet_bf16()
         a, w, present = self.self_attn(self.input_layernorm(hidden_states), attention_mask=attention_mask, position_ids=position_ids,
                                        past_key_value=past_key_value, output_attentions=output_attentions, use_cache=use_cache)
         hidden_states = hidden_states + a
@@ -603,6 +630,7 @@ class LlamaDecoderLayer(DecoderLayer):
             raise ops._lib.LanternError(
                 f"LlamaDecoderLayer: the drafting shape ({tuple(hidden_states.shape)}, bf16, device) takes the fused HIP path, which needs head_dim 64 or "
                 f"128 (got {at.head_dim}), hidden % 64 == 0, silu, bf16 weights / norms and freqs_cis; set `layer.fused = False` for torch's ops")
+        self._no_quiet_bf16()
         residual = hidden_states
         x = hidden_states if self.index == 0 else self.input_layernorm(hidden_states)
         a, w, present = self.self_attn(x, attention_mask=attention_mask, position_ids=position_ids, freqs_cis=freqs_cis, past_key_value=past_key_value,

@@ -652,7 +652,7 @@ class EaLumina_mGPT(MirrorBase, nn.Module):
         return cls.from_reference(ref, cfg_mode=cfg_mode, eagle_version=eagle_version)
 
     @classmethod
-    def from_reference(cls, ref, **kw):
+    def from_reference(cls, ref, drafter_weight_format: str = "bf16", **kw):
         """Wrap a model the reference's own `from_pretrained` loaded (checkpoint loading stays there): same base model, drafter
-        and neighbour table, this package's accept loop."""
-        return cls(ref.base_model, ref.ea_layer, ref.nearest_latents, **kw)
+        and neighbour table, this package's accept loop.  drafter_weight_format = "fp8": the drafter streams e4m3fn weights (MirrorBase.set_drafter_weight_format)."""
+        return cls(ref.base_model, ref.ea_layer, ref.nearest_latents, **kw).set_drafter_weight_format(drafter_weight_format)

@@ -671,26 +671,60 @@ def _sk_workspace(device):
     return ws
 
 
+PACKED_BF16, PACKED_FP8 = 1, 2          # LANTERN_PACKED_* (include/lantern_hip.h): the value of the C-ABI's `packed` arguments
+
+
 class PackedLinearWeight:
     """A [N, K] bf16 nn.Linear weight re-laid out for lantern_linear_rows_streamk (lantern_pack_linear_weight): `data` is the brick stream,
-    `n_rows` / `K` / `pair_rows` describe the original."""
+    `n_rows` / `K` / `pair_rows` describe the original.  `fmt`: "bf16" (the same values), or "fp8" (lantern_pack_linear_weight_fp8: e4m3fn codes
+    with one f32 scale per row behind the bricks -- half the bytes per drafting pass; `data` is then a uint8 tensor)."""
 
-    def __init__(self, data, n_rows, K, pair_rows):
-        self.data, self.n_rows, self.K, self.pair_rows = data, int(n_rows), int(K), int(pair_rows)
+    def __init__(self, data, n_rows, K, pair_rows, fmt="bf16"):
+        self.data, self.n_rows, self.K, self.pair_rows, self.fmt = data, int(n_rows), int(K), int(pair_rows), fmt
+
+    @property
+    def code(self) -> int:
+        """what the `packed` argument of the C-ABI takes for this weight"""
+        return PACKED_FP8 if self.fmt == "fp8" else PACKED_BF16
 
 
-def pack_linear_weight(weight, pair_rows: int = 0) -> PackedLinearWeight:
-    """weight [N, K] bf16 (K % 64 == 0) -> PackedLinearWeight; pair_rows > 0: weight = cat(gate, up) rows, N = 2 * pair_rows."""
+def _packed_code(packed) -> int:
+    return 0 if packed is None else packed.code
+
+
+def pack_linear_weight(weight, pair_rows: int = 0, fmt: str = "bf16") -> PackedLinearWeight:
+    """weight [N, K] bf16 (K % 64 == 0) -> PackedLinearWeight; pair_rows > 0: weight = cat(gate, up) rows, N = 2 * pair_rows.
+    fmt = "fp8": quantised on the device to e4m3fn with a per-row f32 scale (s = max|row| / 448)."""
+    if fmt not in ("bf16", "fp8"):
+        raise _lib.LanternError(f"pack_linear_weight: fmt {fmt!r} (bf16 or fp8)")
     if not weight.is_cuda or weight.dtype != torch.bfloat16 or weight.dim() != 2 or weight.shape[1] % 64:
         raise _lib.LanternError("pack_linear_weight: a [N, K] bf16 device tensor with K % 64 == 0")
     weight = weight.contiguous()
     N, K = weight.shape
     n_rows = pair_rows if pair_rows > 0 else N
     L = _lib.lib()
+    if fmt == "fp8":
+        nbytes = int(L.lantern_pack_linear_weight_fp8_bytes(n_rows, K, pair_rows))
+        out = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+        check(L.lantern_pack_linear_weight_fp8(C.c_void_p(weight.data_ptr()), n_rows, K, int(pair_rows), C.c_void_p(out.data_ptr()), _stream()), "pack_linear_weight_fp8")
+        return PackedLinearWeight(out, n_rows, K, pair_rows, "fp8")
     nbytes = int(L.lantern_pack_linear_weight_bytes(n_rows, K, pair_rows))
     out = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
     check(L.lantern_pack_linear_weight(C.c_void_p(weight.data_ptr()), n_rows, K, int(pair_rows), C.c_void_p(out.data_ptr()), _stream()), "pack_linear_weight")
     return PackedLinearWeight(out, n_rows, K, pair_rows)
+
+
+def unpack_linear_weight_fp8(packed: PackedLinearWeight):
+    """The codes and scales of an fp8 PackedLinearWeight in row-major order: (q [N, K] uint8 -- view as torch.float8_e4m3fn --, scale [N] f32), N the
+    source weight's rows (lantern_unpack_linear_weight_fp8; the byte order inside a brick stays private to the library)."""
+    if not isinstance(packed, PackedLinearWeight) or packed.fmt != "fp8":
+        raise _lib.LanternError("unpack_linear_weight_fp8: an fp8 PackedLinearWeight (pack_linear_weight(.., fmt='fp8'))")
+    N = 2 * packed.pair_rows if packed.pair_rows > 0 else packed.n_rows
+    q = torch.empty((N, packed.K), dtype=torch.uint8, device=packed.data.device)
+    scale = torch.empty((N,), dtype=torch.float32, device=packed.data.device)
+    check(_lib.lib().lantern_unpack_linear_weight_fp8(C.c_void_p(packed.data.data_ptr()), packed.n_rows, packed.K, packed.pair_rows, C.c_void_p(q.data_ptr()),
+                                                      C.c_void_p(scale.data_ptr()), _stream()), "unpack_linear_weight_fp8")
+    return q, scale
 
 
 def linear_rows_streamk(A, weight, epilogue: int = 0, n_rows: Optional[int] = None, bias=None, residual=None, pair_rows: int = 0, row_lo: int = 0):
@@ -720,7 +754,7 @@ def linear_rows_streamk(A, weight, epilogue: int = 0, n_rows: Optional[int] = No
     b = None if bias is None else bias.contiguous()
     check(L.lantern_linear_rows_streamk(C.c_void_p(A.data_ptr()), C.c_void_p(wt.data_ptr()), C.c_void_p(_ptr(b)), M, K, row_lo, n_rows,
                                         C.c_void_p(out.data_ptr()), n_rows, 0, int(epilogue), C.c_void_p(_ptr(r)), 0 if r is None else r.shape[1], int(pair_rows),
-                                        int(packed), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream()), "linear_rows_streamk")
+                                        weight.code if packed else 0, C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream()), "linear_rows_streamk")
     return out
 
 
@@ -735,6 +769,12 @@ def linear_rows_packed(A, weight: "PackedLinearWeight", epilogue: int = 0, bias=
     M, K = A.shape
     if K != weight.K or (epilogue == EPI_SILU_MUL) != (weight.pair_rows > 0):
         raise _lib.LanternError("linear_rows_packed: the packed weight does not match this call (K, gate / up pairing)")
+    if weight.fmt == "fp8":
+        # no tiled fp8 kernel: the rows go through the stream-K kernel in blocks of at most 32 (the prefill runs once per image; cost in EXPERIMENTS.md)
+        if M == 0:
+            return torch.empty((0, weight.n_rows), dtype=torch.bfloat16, device=A.device)
+        return torch.cat([linear_rows_streamk(A[m0:m0 + 32], weight, epilogue, bias=bias, residual=None if residual is None else residual[m0:m0 + 32])
+                          for m0 in range(0, M, 32)], dim=0)
     out = torch.empty((M, weight.n_rows), dtype=torch.bfloat16, device=A.device)
     r = None if residual is None else residual.contiguous()
     b = None if bias is None else bias.contiguous()
@@ -831,7 +871,7 @@ def head_sample(A, weight, row_lo: int, n_cols: int, cfg: float, bias=None, mode
     check(_lib.lib().lantern_head_sample(C.c_void_p(A.contiguous().data_ptr()), C.c_void_p(wt.data_ptr()), C.c_void_p(_ptr(b)), n, K, int(row_lo), int(n_cols), V,
                                          C.c_float(cfg), int(model), C.c_void_p(_ptr(pos)), C.c_int64(pos_base), w, h, newline_id, eos_id, int(top_k_filter),
                                          int(n_draw), C.c_void_p(_ptr(du)), C.c_void_p(_ptr(di)), C.c_void_p(ws.data_ptr()), C.c_void_p(probs.data_ptr()),
-                                         C.c_void_p(tok.data_ptr()), C.c_void_p(prob.data_ptr()), int(packed is not None), C.c_void_p(sk.data_ptr()),
+                                         C.c_void_p(tok.data_ptr()), C.c_void_p(prob.data_ptr()), _packed_code(packed), C.c_void_p(sk.data_ptr()),
                                          C.c_size_t(sk.numel()), _stream()), "head_sample")
     return probs, tok, prob
 
@@ -863,7 +903,7 @@ def head_expand(A, weight, row_lo: int, n_cols: int, cfg: float, bias=None, mode
         check(_lib.lib().lantern_head_expand_streamk(C.c_void_p(A.data_ptr()), C.c_void_p(wt.data_ptr()), C.c_void_p(_ptr(b)), n, K, int(row_lo), int(n_cols), V,
                                                      C.c_float(cfg), int(model), C.c_void_p(_ptr(pos)), C.c_int64(pos_base), w, h, newline_id, eos_id,
                                                      int(top_k_filter), C.c_void_p(_ptr(si)), int(top_k), C.c_void_p(ws.data_ptr()), C.c_void_p(ti.data_ptr()),
-                                                     C.c_void_p(cu.data_ptr()), C.c_void_p(ci.data_ptr()), C.c_void_p(so.data_ptr()), int(packed is not None),
+                                                     C.c_void_p(cu.data_ptr()), C.c_void_p(ci.data_ptr()), C.c_void_p(so.data_ptr()), _packed_code(packed),
                                                      C.c_void_p(sk.data_ptr()), C.c_size_t(sk.numel()), _stream()), "head_expand_streamk")
         return ti, cu, ci, so
     check(_lib.lib().lantern_head_expand(C.c_void_p(A.data_ptr()), C.c_void_p(weight.data_ptr()), C.c_void_p(_ptr(b)), n, K, int(row_lo), int(n_cols), V,
@@ -919,6 +959,11 @@ def drafter_fc(ids, hidden, embed, weight, bias=None, embed_scale: float = 1.0, 
     assert weight.shape == (H, 2 * H) and embed.shape[1] == H and ids.numel() == M
     out = torch.empty((M, H), dtype=torch.bfloat16, device=hidden.device)
     b = None if bias is None else bias.contiguous()
+    if packed is not None and packed.fmt == "fp8" and (M > 32 or H % 64):
+        # fp8 weights exist for the stream-K kernel only: more rows go through it in blocks of 32 (never onto the bf16 row-major weight unnoticed)
+        if H % 64:
+            raise _lib.LanternError(f"drafter_fc: an fp8 packed weight needs H % 64 == 0 (H = {H})")
+        return torch.cat([drafter_fc(ids[m0:m0 + 32], hidden.reshape(M, H)[m0:m0 + 32], embed, weight, bias, embed_scale, packed) for m0 in range(0, M, 32)], dim=0)
     if M <= 32 and H % 64 == 0:
         if packed is not None and (packed.K != 2 * H or packed.n_rows != H or packed.pair_rows):
             raise _lib.LanternError("drafter_fc: the packed weight is not this fc's [H, 2H] weight")
@@ -926,7 +971,7 @@ def drafter_fc(ids, hidden, embed, weight, bias=None, embed_scale: float = 1.0, 
         wt = weight if packed is None else packed.data
         check(_lib.lib().lantern_drafter_fc_streamk(C.c_void_p(ids.data_ptr()), C.c_void_p(hidden.data_ptr()), C.c_void_p(embed.data_ptr()),
                                                     C.c_void_p(wt.data_ptr()), C.c_void_p(_ptr(b)), M, H, embed.shape[0], C.c_float(embed_scale),
-                                                    C.c_void_p(out.data_ptr()), int(packed is not None), C.c_void_p(sk.data_ptr()), C.c_size_t(sk.numel()),
+                                                    C.c_void_p(out.data_ptr()), _packed_code(packed), C.c_void_p(sk.data_ptr()), C.c_size_t(sk.numel()),
                                                     _stream()), "drafter_fc_streamk")
         return out
     check(_lib.lib().lantern_drafter_fc(C.c_void_p(ids.data_ptr()), C.c_void_p(hidden.data_ptr()), C.c_void_p(embed.data_ptr()),

@@ -98,6 +98,20 @@ class MirrorBase:
             cache[cols] = ops.pack_vq_table(self.nearest_latents, cols)
         return cache[cols]
 
+    def set_drafter_weight_format(self, fmt: str):
+        """"bf16" (default) or "fp8": the weight format the drafter's stream-K GEMMs stream (drafters.cnets.Model.set_weight_format).  Only what the drafter
+        proposes -- the accept length -- can change with it: the accept test compares the target's rows against the distribution the drafter really
+        drew from, so the output distribution (and, for greedy decoding, the token stream) is the same."""
+        if fmt not in ("bf16", "fp8"):
+            raise ValueError(f"drafter_weight_format {fmt!r}: bf16 or fp8")
+        setter = getattr(self.ea_layer, "set_weight_format", None)
+        if setter is None:
+            if fmt != "bf16":
+                raise ops._lib.LanternError("drafter_weight_format = 'fp8' needs this package's drafter (lantern_amd.drafters.cnets.Model) as ea_layer")
+            return self
+        setter(fmt)
+        return self
+
     def _uniforms(self) -> UniformFifo:
         if self._fifo is None:
             self._fifo = UniformFifo(self.nearest_latents.device, window=self.uniform_window)

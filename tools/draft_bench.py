@@ -5,7 +5,8 @@ microseconds per cycle and per drafting depth, with the GPU time of the same ker
 `<model>_static`: the static-tree loop (EAGLE v1 -- Lumina's default eagle_version with mc_sim_7b_63, generate_images.py:59; Anole / LlamaGen LANTERN++
 static drafting with naive_extend_57, BASELINE config 4) through StaticDraftPlan: one lantern_head_sample + one lantern_draft_depth per tree level.
 
-usage: draft_bench.py [lumina|anole|llamagen][_static] [cached positions] [cycles]"""
+usage: draft_bench.py [--weight-format bf16|fp8] [lumina|anole|llamagen][_static] [cached positions] [cycles]
+(--weight-format fp8: cnets.Model.set_weight_format("fp8") -- the drafter's fc, layer and head-window GEMMs stream e4m3fn bricks)"""
 import json
 import os
 import sys
@@ -16,7 +17,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 
+from lantern_amd import _lib as _L
 from lantern_amd.drafters import cnets
+
+_KNOBS = _L.tuning_from_env()          # LANTERN_<NAME>=<int> of this tool's environment -> explicit lantern_tuning_set calls
+
+
+def _take_option(name, default, choices=None):
+    """`--name value` anywhere on the command line (removed from sys.argv: the positional arguments keep their places)"""
+    if name in sys.argv:
+        i = sys.argv.index(name)
+        v = sys.argv[i + 1]
+        del sys.argv[i:i + 2]
+        if choices and v not in choices:
+            sys.exit(f"{name}: one of {choices}")
+        return v
+    return default
+
+
+WEIGHT_FORMAT = _take_option("--weight-format", "bf16", ("bf16", "fp8"))
 
 model = sys.argv[1] if len(sys.argv) > 1 else "lumina"
 static = model.endswith("_static")
@@ -41,6 +60,7 @@ if static:
     depth = len(mdl.tree_buffer["tree_indices"])
 else:
     mdl.init_tree()
+mdl.set_weight_format(WEIGHT_FORMAT)
 head = torch.nn.Linear(cfg.hidden_size, cfg.vocab_size, bias=False).to(dev).to(bf)
 H = cfg.hidden_size
 from transformers.generation.logits_process import LogitsProcessorList, TopKLogitsWarper
@@ -79,6 +99,6 @@ e1.record()
 torch.cuda.synchronize()
 wall = (time.perf_counter() - t0) / cycles
 plan = mdl.__dict__.get("_splan" if static else "_plan")
-print(json.dumps({"model": model + ("_static" if static else ""), "tree": (tree_name if static else "EAGLE-2 dynamic"), "one_c_call_per_depth": plan is not None,
+print(json.dumps({"model": model + ("_static" if static else ""), "weight_format": WEIGHT_FORMAT, "tuning": _KNOBS, "tree": (tree_name if static else "EAGLE-2 dynamic"), "one_c_call_per_depth": plan is not None,
                   "levels": ([len(t) for t in mdl.tree_buffer["tree_indices"]] if static else None), "cached_positions": S0, "depth": depth, "us_per_cycle_wall": 1e6 * wall, "us_per_depth_wall": 1e6 * wall / (depth + 1),
                   "us_per_cycle_stream": 1e3 * e0.elapsed_time(e1) / cycles, "drafting_path": type(mdl.layers[0]).__name__}))

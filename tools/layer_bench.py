@@ -1,10 +1,26 @@
 """Drafter decoder layer at Lumina-mGPT-7B size (hidden 4096, 32 heads, intermediate 11008) for one drafting depth (2 x top_k = 20 rows
 against a KV cache): lantern_amd.drafters.decoder_layer on the HIP skinny GEMM vs the same module on torch's bf16 nn.functional.linear.
-Usage: python tools/layer_bench.py [rows_per_stream=10] [past=1200] [out.json]"""
+Usage: python tools/layer_bench.py [--weight-format bf16|fp8] [rows_per_stream=10] [past=1200] [out.json]
+(--weight-format fp8: the layer's four stream-K GEMMs read e4m3fn bricks; the torch side of the comparison keeps the bf16 weights)"""
 import json, os, sys, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from lantern_amd.drafters import decoder_layer as DL
+
+
+def _take_option(name, default, choices=None):
+    """`--name value` anywhere on the command line (removed from sys.argv: the positional arguments keep their places)"""
+    if name in sys.argv:
+        i = sys.argv.index(name)
+        v = sys.argv[i + 1]
+        del sys.argv[i:i + 2]
+        if choices and v not in choices:
+            sys.exit(f"{name}: one of {choices}")
+        return v
+    return default
+
+
+WEIGHT_FORMAT = _take_option("--weight-format", "bf16", ("bf16", "fp8"))
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 past = int(sys.argv[2]) if len(sys.argv) > 2 else 1200
@@ -17,6 +33,7 @@ with torch.no_grad():
     for p in layer.parameters():
         if p.dim() > 1:
             p.copy_(torch.randn_like(p) / p.shape[-1] ** 0.5)
+layer.weight_format = WEIGHT_FORMAT
 x = torch.randn(2, n, 4096, device=dev, dtype=bf)
 kv = (torch.randn(2, 32, past, 128, device=dev, dtype=bf), torch.randn(2, 32, past, 128, device=dev, dtype=bf))
 pos = (past + torch.arange(n, device=dev))[None].expand(2, n).contiguous()
@@ -36,7 +53,7 @@ def timeit(k=50):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / k * 1e3
 
-wbytes = sum(p.numel() * 2 for p in layer.parameters() if p.dim() > 1)
+wbytes = sum(p.numel() * (1 if WEIGHT_FORMAT == "fp8" else 2) for p in layer.parameters() if p.dim() > 1)          # (fp8: + 4 bytes per row of scales, < 0.1 %)
 if os.environ.get("LAYER_BENCH_ONLY") == "tree":
     # the drafting call as cnets.Model.forward issues it (tree block as ancestor words, in-place cache) and nothing else: the profile of
     # this run shows the layer's own kernels only
@@ -51,18 +68,20 @@ if os.environ.get("LAYER_BENCH_ONLY") == "tree":
         with torch.no_grad():
             return layer(x, attention_mask=None, position_ids=pos, past_key_value=prefix, use_cache=True, tree_bits=bits, tree_keys=t1, kv_start=start)[0]
     t = timeit(200)
-    print(json.dumps({"shape": f"rows 2x{n}, past {past}, hidden 4096, heads 32, intermediate 11008 (bf16)", "weight_bytes": wbytes,
+    print(json.dumps({"shape": f"rows 2x{n}, past {past}, hidden 4096, heads 32, intermediate 11008 (bf16)", "weight_format": WEIGHT_FORMAT, "weight_bytes": wbytes,
                       "hip_tree_attention_inplace_cache_us": t, "weight_stream_GBps": wbytes / (t * 1e-6) / 1e9}))
     sys.exit(0)
 y_hip = run().float()
 t_hip = timeit()
 real = DL._hip_ok
 DL._hip_ok = lambda a, w: False
+layer.fused = False          # (the torch composition on the bf16 weights, whatever the weight format of the fused path)
 y_t = run().float()
 t_torch = timeit()
 DL._hip_ok = real
+layer.fused = True
 err = float((y_hip - y_t).abs().max() / y_t.abs().max())
-out = {"shape": f"rows 2x{n}, past {past}, hidden 4096, heads 32, intermediate 11008 (bf16)", "weight_bytes": wbytes,
+out = {"shape": f"rows 2x{n}, past {past}, hidden 4096, heads 32, intermediate 11008 (bf16)", "weight_format": WEIGHT_FORMAT, "weight_bytes": wbytes,
        "hip_skinny_gemm_us": t_hip, "torch_linear_us": t_torch, "speedup": t_torch / t_hip,
        "weight_stream_GBps_hip": wbytes / (t_hip * 1e-6) / 1e9, "frac_of_8TBps_hip": wbytes / (t_hip * 1e-6) / 1e9 / 8000.0,
        "weight_stream_GBps_torch": wbytes / (t_torch * 1e-6) / 1e9, "max_rel_diff_between_the_two": err,

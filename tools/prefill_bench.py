@@ -1,12 +1,28 @@
 """The drafter's prompt prefill (first call of topK_generate: the whole prompt through cnets.Model.forward) at the 7B layer size: the HIP path
 (drafter_fc slices, lantern_linear_rows_packed, head stage, block-causal lantern_tree_attention) against the same model on torch's ops
 (F.linear = hipBLASLt, eager softmax attention under the additive mask), milliseconds per call between HIP events.
-usage: prefill_bench.py [prompt tokens=600] [reps=5]"""
+usage: prefill_bench.py [--weight-format bf16|fp8] [prompt tokens=600] [reps=5]
+(--weight-format fp8: there is no tiled fp8 kernel -- the prefill's GEMMs go through the stream-K kernel in blocks of 32 rows)"""
 import json, os, sys, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from lantern_amd.drafters import cnets, decoder_layer
+
+
+def _take_option(name, default, choices=None):
+    """`--name value` anywhere on the command line (removed from sys.argv: the positional arguments keep their places)"""
+    if name in sys.argv:
+        i = sys.argv.index(name)
+        v = sys.argv[i + 1]
+        del sys.argv[i:i + 2]
+        if choices and v not in choices:
+            sys.exit(f"{name}: one of {choices}")
+        return v
+    return default
+
+
+WEIGHT_FORMAT = _take_option("--weight-format", "bf16", ("bf16", "fp8"))
 
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 600
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -16,6 +32,7 @@ cfg = types.SimpleNamespace(vocab_size=65536, hidden_size=4096, pad_token_id=Non
 torch.manual_seed(0)
 mdl = cnets.Model(cfg, total_tokens=59, depth=5, top_k=10, model_type="lumina_mgpt").to(dev).to(bf)
 mdl.init_tree()
+mdl.set_weight_format(WEIGHT_FORMAT)
 x = torch.randn(2, T, 4096, device=dev, dtype=bf)
 ids = torch.randint(4, 8000, (2, T), device=dev)
 am = torch.ones(2, T, dtype=torch.bool, device=dev)
@@ -49,5 +66,5 @@ decoder_layer._hip_ok = lambda a, b: False
 ms_torch, y_torch = timed()
 w_bytes = sum(p.numel() * 2 for p in mdl.layers[0].parameters())
 flops = 2 * 2 * T * (w_bytes // 2)
-print(json.dumps({"rows": 2 * T, "ms_hip": round(ms_hip, 3), "ms_torch_ops": round(ms_torch, 3), "layer_weight_MB": round(w_bytes / 1e6, 1),
+print(json.dumps({"rows": 2 * T, "weight_format": WEIGHT_FORMAT, "ms_hip": round(ms_hip, 3), "ms_torch_ops": round(ms_torch, 3), "layer_weight_MB": round(w_bytes / 1e6, 1),
                   "layer_gemm_TFLOPs_hip": round(flops / ms_hip / 1e9, 1), "max_abs_diff_valid_rows": float((y_hip[:, 9:].float() - y_torch[:, 9:].float()).abs().max())}))
