@@ -59,7 +59,7 @@ const char *lantern_last_error(void);
 /* Tuning values: kernel-instance / launch-shape choices a MEASUREMENT may override (tools/, a few tests).  The library reads no environment
  * variable; every product path runs the defaults.  Names (defaults): epw_tp (5), epw_tp4 (1), epw_tp_raw (256), epw_spec (2), epw_occ2 (-1),
  * o7_nt (0), prep_nt (0), kv_u (0), kv_ks (4), kv_variant (0), gemm_tiled_from (129), sk_groups (0), sk_whole_mb (40), sk_nt_min_mb (80),
- * ta_splits (0), ta_min_tiles (2), epw_tp_lg (1), epw_fused_helpers (1) -- meanings beside `enum Tuning` in lantern_amd/csrc/common.h.  Process-wide, atomic ints; set before the
+ * ta_splits (0), ta_min_tiles (2), epw_tp_lg (1), epw_fused_helpers (1) -- meanings beside the slots in lantern_amd/csrc/tuning_slots.h.  Process-wide, atomic ints; set before the
  * launches they should affect.  The reference has no counterpart (it has no kernels to choose between). */
 int lantern_tuning_set(const char *name, int value);
 int lantern_tuning_get(const char *name, int *value);
@@ -315,6 +315,14 @@ typedef struct lantern_ep_window {
 #define LANTERN_ST_TREE_LIMIT 7
 int lantern_evaluate_posterior_window(const lantern_ep_params *prm, const lantern_ep_buffers *buf,
                                       const lantern_ep_window *win, void *stream);
+/* Which instance of the chain kernel lantern_evaluate_posterior_window would launch for these argument blocks under the current tuning values
+ * (fused != 0: the chain launch of a LANTERN_STEP_FUSED_PREPARE group; only its checks on these three blocks are applied, the prepare stage's own
+ * arguments are checked by the launch).  Read-only: runs the launch's argument checks and its selection, launches nothing and dereferences no
+ * device pointer.  name[cap] receives the instance as a profiler prints it, e.g. "epw_kernel<256,8,2,4,true,false,2,205>" (empty for B = 0);
+ * returns what the launch would: LANTERN_E_INVALID / LANTERN_E_UNSUPPORTED with the launch's message, LANTERN_E_LAUNCH if the selected instance
+ * is not built into the library, LANTERN_E_INVALID if cap is too small. */
+int lantern_evaluate_posterior_window_instance(const lantern_ep_params *prm, const lantern_ep_buffers *buf,
+                                               const lantern_ep_window *win, int fused, char *name, int cap);
 
 /* ------------------------------------------------------------------------------------
  * O8 node-parallel (v3): the same relaxed rejection sampling, one workgroup per INTERNAL TREE NODE instead of one
@@ -632,7 +640,7 @@ int lantern_linear_rows_splitk(const void *A, const void *W, const void *bias, i
                                const void *residual, int residual_stride, int ksplit, float *workspace, void *stream);
 /* The same products (epilogue 0: bias only, LANTERN_EPI_RESIDUAL, LANTERN_EPI_SILU_MUL) in stream-K form, ONE launch, deterministic: the (tile, K)
  * space is cut into equal contiguous shares, one per workgroup, one workgroup per CU of the current device (hipDeviceAttributeMultiprocessorCount;
- * the LANTERN_SK_GROUPS environment variable overrides the count for tuning runs only), a tile's partial sums meet in the workspace and the
+ * lantern_tuning_set("sk_groups", n) overrides the count for tuning runs only), a tile's partial sums meet in the workspace and the
  * workgroup that completes a tile adds them in K order and runs the epilogue; two trips of loads in flight per wave.  The form the decoder layer
  * uses at its decode shape (M <= 32).  workspace: [dev] lantern_linear_rows_streamk_workspace(n_rows) bytes, 16-byte aligned, zero-filled ONCE
  * by the caller (the kernel leaves its counters zeroed); one launch at a time per workspace. */

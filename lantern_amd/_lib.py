@@ -219,7 +219,7 @@ EXPORTS = [
     "lantern_expand_dynamic", "lantern_gather_candidates", "lantern_cfg_mask_topk",
     "lantern_evaluate_posterior_workspace", "lantern_evaluate_posterior", "lantern_evaluate_posterior_greedy",
     "lantern_kv_gather", "lantern_accept_gather", "lantern_sample_static", "lantern_drafter_fc",
-    "lantern_build_vq_table", "lantern_cfg_mask_topk_window", "lantern_evaluate_posterior_window",
+    "lantern_build_vq_table", "lantern_cfg_mask_topk_window", "lantern_evaluate_posterior_window", "lantern_evaluate_posterior_window_instance",
     "lantern_window_to_dense", "lantern_pack_vq_table", "lantern_update_inference_inputs", "lantern_profile_next_launch", "lantern_drafter_attention_mask", "lantern_linear_rows",
     "lantern_tree_attention_workspace", "lantern_tree_attention",
     "lantern_tree_node_tables_size", "lantern_tree_node_tables", "lantern_evaluate_posterior_nodes_workspace",

@@ -1,7 +1,8 @@
 // epw_body.h -- the windowed chain kernel of evaluate_posterior (O8): one workgroup per sequence (epw_body / epw_kernel), shared by the
 // translation units that instantiate it (window_kernels.hip: the latency instances of the fixed configurations; epw_generic.hip: the
 // argument-driven instances for any window / table form; epw_throughput.hip: the forms for more sequences per launch than CUs) -- three
-// files so that the ~55 instances of this 800-line template compile side by side.
+// files so that the 73 instances of this 800-line template compile side by side.  Each file lists its instances once (EPW_CHAIN, at the end of
+// this header); epw_config.h says what a SPEC assumes and names the TPO bits; epw_select (window_kernels.hip) picks the instance of a launch.
 //
 // Reference: models/ea_model_lumina_mgpt.py:610-726 (O8), :781 (bonus token); models/ea_model_llamagen.py:597-669,709-787.
 #pragma once
@@ -9,6 +10,7 @@
 #include "window_dev.h"
 #include "tree_dynamic_dev.h"
 #include "prep_dev.h"
+#include "epw_config.h"
 
 // in-kernel phase stamps: only the diagnostic build of window_kernels.hip defines them (-DEPW_TRACE); nothing everywhere else
 #ifndef EPW_STAMP
@@ -163,29 +165,29 @@ __device__ __forceinline__ void epw_helper_row(const EpwFused &f, const int hx) 
 
 template <int NT, int E4, int IDMODE, int WPE, bool FULLW = false, bool RAW = false, int SPEC = 0, int TPO = 0>
 __device__ __forceinline__ int epw_body(const EpwArgs &args, const int b, const EpwFused *fz = nullptr) {
-    constexpr bool NUCLEUS = (TPO & 2) != 0;         // raw rows: TopPLogitsWarper (prm.top_p) in front of the top-k of the rows the walk post-processes
-    constexpr bool LATE_Q = (TPO & 1) != 0;          // throughput builds: a candidate's drafter row is requested once its rejection is known (an accepted
+    constexpr bool NUCLEUS = (TPO & EPW_NUCLEUS) != 0;         // raw rows: TopPLogitsWarper (prm.top_p) in front of the top-k of the rows the walk post-processes
+    constexpr bool LATE_Q = (TPO & EPW_LATE_Q) != 0;          // throughput builds: a candidate's drafter row is requested once its rejection is known (an accepted
                                                      // candidate -- 0.65 of the first tries -- then costs no row request at all; the latency is another workgroup's problem)
     static_assert(!RAW || (FULLW && (E4 == 4 || E4 == 8)), "raw rows: W = 4 * E4 * NT ids, E4 / 2 sixteen-byte chunks of cond and of uncond per thread");
     constexpr int CH = E4 / 2 > 0 ? E4 / 2 : 1;          // raw rows: 8-id chunks per thread and operand
-    constexpr bool ROTW = (TPO & 8) != 0;            // throughput builds: the wave that runs a sequence's serial section rotates with the sequence (b % NW) instead of
+    constexpr bool ROTW = (TPO & EPW_ROTW) != 0;            // throughput builds: the wave that runs a sequence's serial section rotates with the sequence (b % NW) instead of
                                                      // always being wave 0 -- four workgroups share a CU, and their serial sections then sit on different SIMDs
-    constexpr bool ALLW = (TPO & 16) != 0;           // throughput builds: the k-neighbour cumulative-mass scan on ALL waves (EW_PF_K / NT neighbours per lane, one DPP scan per
+    constexpr bool ALLW = (TPO & EPW_ALLW) != 0;           // throughput builds: the k-neighbour cumulative-mass scan on ALL waves (EW_PF_K / NT neighbours per lane, one DPP scan per
                                                      // wave, the waves' totals exchanged through LDS) and the decision computed by every wave -- no serial section at all
-    constexpr bool LDS2P = (TPO & 64) != 0;          // the residual of a rejection goes back to LDS unnormalised and is normalised by a second pass over LDS: no 8-float4
+    constexpr bool LDS2P = (TPO & EPW_LDS2P) != 0;          // the residual of a rejection goes back to LDS unnormalised and is normalised by a second pass over LDS: no 8-float4
                                                      // register copy of the window lives across the reduction (the four-per-CU build sits at its 128-VGPR cap)
-    constexpr bool PRIO = (TPO & 128) != 0;          // the serial section runs at raised wave priority (s_setprio): four workgroups share a CU, and a sequence's progress is gated
+    constexpr bool PRIO = (TPO & EPW_PRIO) != 0;          // the serial section runs at raised wave priority (s_setprio): four workgroups share a CU, and a sequence's progress is gated
                                                      // by its one serial wave while the other workgroups' W-wide passes compete for the same SIMD's issue slots
-    constexpr bool COMPACT = (TPO & 4) != 0;         // the default tree's throughput build on the smallest staged tables (EwSharedCompact, no neighbour
+    constexpr bool COMPACT = (TPO & EPW_COMPACT) != 0;         // the default tree's throughput build on the smallest staged tables (EwSharedCompact, no neighbour
                                                      // bit mask, 2 prefetch slots): 40 KB of LDS, four workgroups per CU
-    static_assert(!COMPACT || (SPEC == 2 && !RAW), "the compact tables are sized for the reference's default tree mc_sim_7b_63 on probability rows");
-    constexpr bool LITE = (TPO & 256) != 0;          // LlamaGen's throughput build: the 64 KB window leaves 14 KB for everything else if TWO workgroups are to share a CU --
+    static_assert(!COMPACT || (SPEC == EPW_SPEC_LUMINA_DEFAULT_TREE && !RAW), "the compact tables are sized for the reference's default tree mc_sim_7b_63 on probability rows");
+    constexpr bool LITE = (TPO & EPW_LITE) != 0;          // LlamaGen's throughput build: the 64 KB window leaves 14 KB for everything else if TWO workgroups are to share a CU --
                                                      // EwSharedLite (trees of <= 64 nodes, no neighbour lists: LANTERN off), no neighbour bit mask
-    static_assert(!LITE || (SPEC == 5 && !RAW && !COMPACT), "the lite tables: LlamaGen's standard verify (dynamic trees, LANTERN off) on probability rows");
-    constexpr bool DMAROW = COMPACT || (TPO & 512) != 0;          // probability rows land in g by LDS-DMA (row_dma_to_lds): no VGPR staging, no ds_write pass
-    static_assert(!DMAROW || (SPEC >= 1 && !RAW && FULLW), "LDS-DMA rows: final probability rows of a fixed configuration whose window is the workgroup's tile");
-    constexpr bool FUSED = (TPO & 1024) != 0;        // the prepare stage rides in this launch (EpwFused above): candidates assembled here, listed rows taken when published
-    static_assert(!FUSED || (RAW && (SPEC == 1 || SPEC == 2 || SPEC == 4) && WPE == 1), "fused prepare: the static-tree latency instances (Lumina, Anole) on raw rows");
+    static_assert(!LITE || (SPEC == EPW_SPEC_LLAMAGEN_DYNAMIC && !RAW && !COMPACT), "the lite tables: LlamaGen's standard verify (dynamic trees, LANTERN off) on probability rows");
+    constexpr bool DMAROW = COMPACT || (TPO & EPW_DMAROW) != 0;          // probability rows land in g by LDS-DMA (row_dma_to_lds): no VGPR staging, no ds_write pass
+    static_assert(!DMAROW || (SPEC != EPW_SPEC_GENERIC && !RAW && FULLW), "LDS-DMA rows: final probability rows of a fixed configuration whose window is the workgroup's tile");
+    constexpr bool FUSED = (TPO & EPW_FUSED) != 0;        // the prepare stage rides in this launch (EpwFused above): candidates assembled here, listed rows taken when published
+    static_assert(!FUSED || (RAW && (SPEC == EPW_SPEC_LUMINA_STATIC || SPEC == EPW_SPEC_LUMINA_DEFAULT_TREE || SPEC == EPW_SPEC_ANOLE_STATIC) && WPE == 1), "fused prepare: the static-tree latency instances (Lumina, Anole) on raw rows");
     typedef typename std::conditional<COMPACT, EwSharedCompact, typename std::conditional<LITE, EwSharedLite, EwShared>::type>::type SH;
     constexpr int MAX_B = SH::kMaxB, MAX_N = SH::kMaxN, N_UNI = SH::kUni;
     constexpr bool LDSIDS = IDMODE != 0;
@@ -199,20 +201,14 @@ __device__ __forceinline__ int epw_body(const EpwArgs &args, const int b, const 
     extern __shared__ float4 dyn_lds[];
     float *g = reinterpret_cast<float *>(dyn_lds);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // Compile-time instances of the reference's configurations (SPEC 0: everything from the argument block).  They all share the Chameleon
-    // vocabulary of Lumina-mGPT / Anole (V = 65536, image ids = window = [4, 8196), table offset 4, 8192 table rows):
-    //   1  Lumina static tree (LANTERN_MODE_STATIC_LUMINA), LANTERN on, syntax shortcut with Lumina's four syntax ids
-    //   2  = 1 + the reference's default Lumina tree mc_sim_7b_63 (26 nodes, 15 paths of depth <= 6; run.sh / generate_images.py)
-    //   3  Lumina dynamic (EAGLE-2) trees: LANTERN_MODE_DYNAMIC, LANTERN on, syntax shortcut, per-sequence paths / depths / positions
-    //   4  Anole static tree (LANTERN_MODE_STATIC_LG: the neighbour set zeroes q), LANTERN on, no syntax shortcut
-    //   5  LlamaGen dynamic (EAGLE-2) trees, standard verify (BASELINE config 2): LANTERN off, no syntax shortcut, V = window = 16384 ids from 0
-    // The mode / flag tests below fold away, and with them the scalar registers that carried them through the whole walk; the host
-    // dispatches to an instance only when the argument block says exactly that.
-    constexpr bool SL = SPEC >= 1;                               // one of the fixed configurations
-    constexpr bool S_STATIC = SPEC == 1 || SPEC == 2 || SPEC == 4, S_DYN = SPEC == 3 || SPEC == 5, S_SYN = SPEC >= 1 && SPEC <= 3;
-    constexpr bool S_LG = SPEC == 5;                             // LlamaGen's vocabulary instead of Chameleon's
-    const int Ps = (SPEC == 2) ? 15 : prm.P, Ds = (SPEC == 2) ? 6 : prm.D, V = SL ? (S_LG ? 16384 : 65536) : prm.V, W = SL ? (S_LG ? 16384 : 8192) : win.win_len,
-              lo = SL ? (S_LG ? 0 : 4) : win.win_lo;
+    // Compile-time instances of the reference's configurations (epw_config.h: EpwSpecId names them, kEpwSpec[SPEC] says what each assumes; SPEC 0:
+    // everything from the argument block).  The mode / flag tests below fold away, and with them the scalar registers that carried them through
+    // the whole walk; the host takes an instance only when epw_spec_matches() -- written against the same record -- says the argument block is that.
+    constexpr EpwSpec CF = kEpwSpec[SPEC];
+    constexpr bool SL = SPEC != EPW_SPEC_GENERIC;                // one of the fixed configurations
+    constexpr bool S_DYN = SL && CF.mode == LANTERN_MODE_DYNAMIC, S_STATIC = SL && !S_DYN;
+    constexpr bool S_TREE = SL && CF.P != 0;                     // ... on a fixed tree
+    const int Ps = S_TREE ? CF.P : prm.P, Ds = S_TREE ? CF.D : prm.D, V = SL ? CF.V : prm.V, W = SL ? CF.win_len : win.win_len, lo = SL ? CF.win_lo : win.win_lo;
     uint32_t *nbmask = reinterpret_cast<uint32_t *>(g + W + EW_G_EXT);  // W bits: neighbour set (static LlamaGen/Anole: zeroing hits q); not allocated when COMPACT
     SH &S = *reinterpret_cast<SH *>(reinterpret_cast<char *>(g) + epw_shared_offset(W, !(COMPACT || LITE)));
     int *const Scand = reinterpret_cast<int *>(reinterpret_cast<char *>(&S) + sizeof(SH));
@@ -221,14 +217,14 @@ __device__ __forceinline__ int epw_body(const EpwArgs &args, const int b, const 
     float *const Scart = reinterpret_cast<float *>(Sboff + pd_cap);
     int *const Sflag = reinterpret_cast<int *>(Scart + pd_cap);       // per (path, depth): bit 1 image token, bit 0 syntax token
     int *const Shist = Sflag + pd_cap;                                // RAW: the radix-select histograms of the row post-process; logit rows with top_p: its 256 f64 mass bins
-    const int k = prm.k, off = SL ? (S_LG ? 0 : 4) : prm.tok_offset;
-    const int p_mode = !SL ? prm.mode : (SPEC == 4 ? (int)LANTERN_MODE_STATIC_LG : (S_DYN ? (int)LANTERN_MODE_DYNAMIC : (int)LANTERN_MODE_STATIC_LUMINA));
-    const bool p_lantern = SL ? !S_LG : prm.lantern != 0;
-    const bool p_syntax = SL ? S_SYN : prm.syntax_shortcut != 0;
-    const int p_nsyn = SL ? (S_SYN ? 4 : 0) : prm.n_syntax;
-    const int p_rows = (SPEC == 2) ? 26 : prm.rows_per_seq, p_N = (SPEC == 2) ? 26 : prm.N;
-    const int p_img_lo = SL ? (S_LG ? 0 : 4) : prm.img_lo, p_img_hi = SL ? (S_LG ? 16384 : 8196) : prm.img_hi, p_trows = SL ? (S_LG ? 0 : 8192) : prm.table_rows;
-    auto p_syn = [&](int q) -> int { return SL ? (q == 0 ? 8196 : (q == 1 ? 8197 : (q == 2 ? 8803 : 8828))) : prm.syntax[q]; };
+    const int k = prm.k, off = SL ? CF.tok_offset : prm.tok_offset;
+    const int p_mode = SL ? CF.mode : prm.mode;
+    const bool p_lantern = SL ? CF.lantern : prm.lantern != 0;
+    const bool p_syntax = SL ? CF.syntax_shortcut : prm.syntax_shortcut != 0;
+    const int p_nsyn = SL ? (CF.syntax_shortcut ? 4 : 0) : prm.n_syntax;
+    const int p_rows = S_TREE ? CF.rows_per_seq : prm.rows_per_seq, p_N = S_TREE ? CF.N : prm.N;
+    const int p_img_lo = SL ? CF.img_lo : prm.img_lo, p_img_hi = SL ? CF.img_hi : prm.img_hi, p_trows = SL ? CF.table_rows : prm.table_rows;
+    auto p_syn = [&](int q) -> int { return SL ? (q == 0 ? CF.syntax[0] : (q == 1 ? CF.syntax[1] : (q == 2 ? CF.syntax[2] : CF.syntax[3]))) : prm.syntax[q]; };
     const bool is_static = SL ? S_STATIC : p_mode != LANTERN_MODE_DYNAMIC;
     const int P = S_DYN ? buf.n_paths[b] : ((!SL && buf.n_paths) ? buf.n_paths[b] : Ps);
     const int D = S_DYN ? buf.n_depth[b] : ((!SL && buf.n_depth) ? buf.n_depth[b] : Ds);
@@ -341,13 +337,13 @@ __device__ __forceinline__ int epw_body(const EpwArgs &args, const int b, const 
             }
             // the row's class from its position (MultiModalLogitsProcessor, ea_model_lumina_mgpt.py:45-86); raw_w_latent == 0: a model without
             // grammar rows (LlamaGen: every row is an ordinary distribution)
-            if (RAW && !S_LG && t < p_rows && win.raw_w_latent > 0) {
+            if (RAW && !(SL && CF.eos_id < 0) && t < p_rows && win.raw_w_latent > 0) {
                 const int64_t n1 = ((SL ? (int)S_DYN : win.raw_pos_per_seq) ? win.raw_pos_ids[(size_t)b * p_rows + t] : win.raw_pos_ids[t] + win.raw_seq_len[b]) - win.raw_pos_base + 1;
                 // (a 64-bit modulo is ~150 instructions: the 32-bit form whenever the operands fit -- always, for real image sizes)
                 const bool fits = n1 >= 0 && n1 < (1ll << 31) && win.raw_w_latent >= 0 && win.raw_w_latent < (1 << 30);
                 const bool nl = (fits ? ((uint32_t)n1 % (uint32_t)(win.raw_w_latent + 1)) == 0u : py_mod64(n1, (int64_t)win.raw_w_latent + 1) == 0);
-                hot_[u] = (n1 == ((int64_t)win.raw_w_latent + 1) * win.raw_h_latent + 1) ? (SL ? 8196 : win.raw_eos_id)
-                          : (nl ? (SL ? 8803 : win.raw_newline_id) : -1);
+                hot_[u] = (n1 == ((int64_t)win.raw_w_latent + 1) * win.raw_h_latent + 1) ? (SL ? CF.eos_id : win.raw_eos_id)
+                          : (nl ? (SL ? CF.newline_id : win.raw_newline_id) : -1);
             }
         }
         if (is_static && tid < Ds - 1) oo_ = buf.op_off[tid];
@@ -459,12 +455,12 @@ __device__ __forceinline__ int epw_body(const EpwArgs &args, const int b, const 
         // neighbour ids of the level's candidates: their HBM reads are issued first, the row's loads second; both are in
         // flight together and the ids are written to LDS under the row's last barrier (one exposed latency per level)
         constexpr int PF_PER = (EW_PF_K + NT - 1) / NT;
-        constexpr int PF_LIST = COMPACT ? 2 : (SPEC == 2 ? 4 : EW_PF_C);          // candidates per level staged ahead (the others restage a slot when their turn comes)
+        constexpr int PF_LIST = COMPACT ? 2 : (S_TREE ? CF.fan_out : EW_PF_C);          // candidates per level staged ahead (the others restage a slot when their turn comes)
         // position t of a neighbour list -> index into g for the scan (out_tok is final before the ids are staged)
         auto plain_addr = [&](int id) -> unsigned short {
             // the Chameleon configurations: the table's ids ARE window indices (ids 0..8191 + offset 4 = the window [4, 8196)): no range test, no
             // out-of-window token can be a neighbour (masked, so that a corrupt table entry still lands inside g)
-            if constexpr (SL && !S_LG) return (unsigned short)(id & 8191);
+            if constexpr (SL && CF.lantern && CF.table_rows == CF.win_len && CF.tok_offset == CF.win_lo) return (unsigned short)(id & (CF.win_len - 1));
             const int e = id + off;
             if (e >= lo && e < lo + W) return (unsigned short)(e - lo);
             return (unsigned short)(W + (e == out_tok ? EW_G_OUT : EW_G_ZERO));
@@ -1199,29 +1195,48 @@ __global__ __launch_bounds__(NT, WPE) void epw_kernel_fused(const EpwArgs args, 
         epw_helper_row<NT, E4 / 2>(fz, (int)blockIdx.x);
         return;
     }
-    epw_body<NT, E4, IDMODE, WPE, FULLW, RAW, SPEC, TPO | 1024>(args, (int)blockIdx.x - fz.n_helpers, &fz);
+    epw_body<NT, E4, IDMODE, WPE, FULLW, RAW, SPEC, TPO | EPW_FUSED>(args, (int)blockIdx.x - fz.n_helpers, &fz);
 }
 
-// One launch of the chain kernel: what the instance files need besides the argument block.
+// One launch of the chain kernel: what an instance needs besides the argument block.
 struct EpwLaunch {
     dim3 grid;
     size_t lds;
     hipStream_t st;
 };
-// epw_generic.hip: the argument-driven instances (SPEC 0, one workgroup per CU) by window width / id mode; nucleus: TopPLogitsWarper inside the
-// kernel for rows that arrive as logits (LANTERN_ROWS_LOGITS, prm.top_p).  Returns false when no instance fits.
-bool epw_launch_generic(int W, int idmode, bool nucleus, const EpwLaunch &l, const EpwArgs &args);
-// epw_throughput.hip: the forms for more sequences per launch than CUs (several workgroups per CU).
-enum EpwThroughput {
-    EPW_TP_LUMINA_DEFAULT_TREE = 0, EPW_TP_LUMINA_STATIC, EPW_TP_LUMINA_DYNAMIC, EPW_TP_ANOLE_STATIC,      // 256 threads x 8 float4, three per CU, LATE_Q
-                                                                                                             // (the default tree: COMPACT, four per CU)
-    EPW_TP_512_DEFAULT_TREE, EPW_TP_512_PACKED, EPW_TP_512_ID0, EPW_TP_512_ID1, EPW_TP_512_ID2,            // 512 threads at 128 VGPRs, two per CU
-    EPW_TP_RAW_GENERIC,                                                                                      // raw rows, 512 threads, two per CU
-    EPW_TP_RAW_LUMINA_DEFAULT_TREE, EPW_TP_RAW_LUMINA_STATIC, EPW_TP_RAW_LUMINA_DYNAMIC, EPW_TP_RAW_ANOLE_STATIC,   // raw rows, fixed configurations
-    EPW_TP_RAW_LLAMAGEN_DYNAMIC,                                                                             // LlamaGen's 16384-id window, raw rows
-    EPW_TP_LLAMAGEN_DYNAMIC                                                                                  // LlamaGen's 16384-id window, probability rows: 512 threads x 8 float4, two per CU
-};
-bool epw_launch_throughput(int kind, const EpwLaunch &l, const EpwArgs &args);
 
+// An instance by its template arguments (`fused`: epw_kernel_fused instead of epw_kernel), as the profiler prints them.
+struct EpwKey {          // (all ints: two keys compare as bytes)
+    int fused, nt, e4, idmode, wpe, fullw, raw, spec, tpo;
+};
+struct EpwInstance {
+    EpwKey key;
+    void (*launch)(const EpwLaunch &, const EpwArgs &, const EpwFused *);
+};
+template <int NT, int E4, int IDMODE, int WPE, bool FULLW, bool RAW, int SPEC, int TPO>
+void epw_launch_chain(const EpwLaunch &l, const EpwArgs &args, const EpwFused *) {
+    LANTERN_LAUNCH((epw_kernel<NT, E4, IDMODE, WPE, FULLW, RAW, SPEC, TPO>), l.grid, dim3(NT), l.lds, l.st, args);
+}
+template <int NT, int E4, int IDMODE, int WPE, bool FULLW, bool RAW, int SPEC, int TPO>
+void epw_launch_fused(const EpwLaunch &l, const EpwArgs &args, const EpwFused *fz) {
+    LANTERN_LAUNCH((epw_kernel_fused<NT, E4, IDMODE, WPE, FULLW, RAW, SPEC, TPO>), l.grid, dim3(NT), l.lds, l.st, args, *fz);
+}
+// Every instance is named exactly once, as an EPW_CHAIN / EPW_FUSED entry of the list of the translation unit that owns it: the entry both instantiates
+// the kernel and makes it launchable by key.  Which launch gets which key is epw_select's business (window_kernels.hip) and nobody else's.
+#define EPW_CHAIN(NT, E4, IDMODE, WPE, FULLW, RAW, SPEC, TPO) \
+    {{false, NT, E4, IDMODE, WPE, FULLW, RAW, SPEC, TPO}, &epw_launch_chain<NT, E4, IDMODE, WPE, FULLW, RAW, SPEC, TPO>},
+#define EPW_FUSED_ENTRY(NT, E4, IDMODE, WPE, FULLW, RAW, SPEC, TPO) \
+    {{true, NT, E4, IDMODE, WPE, FULLW, RAW, SPEC, TPO}, &epw_launch_fused<NT, E4, IDMODE, WPE, FULLW, RAW, SPEC, TPO>},
+struct EpwInstanceList {
+    const EpwInstance *v;
+    int n;
+};
+// window_kernels.hip: the latency instances of the fixed configurations (one workgroup per CU) and the fused-prepare instances;
+// epw_generic.hip: the argument-driven instances (SPEC 0) by window width / id mode, with and without TopPLogitsWarper inside the kernel;
+// epw_throughput.hip: the forms for more sequences per launch than CUs (several workgroups per CU).
+// (each list is a host function's static table: a namespace-scope constant would be emitted for the device too, where the launch functions do not exist)
+EpwInstanceList epw_latency_instances();
+EpwInstanceList epw_generic_instances();
+EpwInstanceList epw_throughput_instances();
 
 }  // namespace lantern

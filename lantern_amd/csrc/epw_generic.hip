@@ -7,26 +7,14 @@
 
 namespace lantern {
 
-template <int NT, int E4, int TPO>
-static void launch_ids(int idmode, const EpwLaunch &l, const EpwArgs &args) {
-    if (idmode == 2) LANTERN_LAUNCH((epw_kernel<NT, E4, 2, 1, false, false, 0, TPO>), l.grid, dim3(NT), l.lds, l.st, args);
-    else if (idmode == 1) LANTERN_LAUNCH((epw_kernel<NT, E4, 1, 1, false, false, 0, TPO>), l.grid, dim3(NT), l.lds, l.st, args);
-    else LANTERN_LAUNCH((epw_kernel<NT, E4, 0, 1, false, false, 0, TPO>), l.grid, dim3(NT), l.lds, l.st, args);
-}
-
-template <int TPO>
-static bool launch_width(int W, int idmode, const EpwLaunch &l, const EpwArgs &args) {
-    if (W <= 1024) launch_ids<256, 1, TPO>(idmode, l, args);
-    else if (W <= 2048) launch_ids<256, 2, TPO>(idmode, l, args);
-    else if (W <= 4096) launch_ids<512, 2, TPO>(idmode, l, args);
-    else if (W <= 8192) launch_ids<512, 4, TPO>(idmode, l, args);
-    else if (W <= 16384) launch_ids<1024, 4, TPO>(idmode, l, args);
-    else return false;
-    return true;
-}
-
-bool epw_launch_generic(int W, int idmode, bool nucleus, const EpwLaunch &l, const EpwArgs &args) {
-    return nucleus ? launch_width<2>(W, idmode, l, args) : launch_width<0>(W, idmode, l, args);
+// threads x float4 per thread by window width (<= 1024, 2048, 4096, 8192, 16384 ids: epw_select's generic()), each for the three neighbour-id modes
+#define EPW_GENERIC_IDS(NT, E4, TPO) \
+    EPW_CHAIN(NT, E4, 2, 1, false, false, EPW_SPEC_GENERIC, TPO) EPW_CHAIN(NT, E4, 1, 1, false, false, EPW_SPEC_GENERIC, TPO) EPW_CHAIN(NT, E4, 0, 1, false, false, EPW_SPEC_GENERIC, TPO)
+#define EPW_GENERIC_WIDTHS(TPO) \
+    EPW_GENERIC_IDS(256, 1, TPO) EPW_GENERIC_IDS(256, 2, TPO) EPW_GENERIC_IDS(512, 2, TPO) EPW_GENERIC_IDS(512, 4, TPO) EPW_GENERIC_IDS(1024, 4, TPO)
+EpwInstanceList epw_generic_instances() {
+    static const EpwInstance k[] = {EPW_GENERIC_WIDTHS(EPW_NUCLEUS) EPW_GENERIC_WIDTHS(0)};
+    return {k, (int)(sizeof(k) / sizeof(k[0]))};
 }
 
 }  // namespace lantern

@@ -11,6 +11,7 @@
 // as epw_kernel, operation for operation (shared helpers: window_dev.h), so both produce the same bits.
 #include "common.h"
 #include "window_dev.h"
+#include "epw_config.h"
 
 namespace lantern {
 
@@ -72,8 +73,8 @@ struct EpnVerdict {
 
 // The routine of ONE node: try its children in order against the node's row (see the header).  `sw`: the node's packed header
 // (EpnStatic), `ri`: its rank among the internal nodes (0 for a leaf), `uoff`: uniforms the walk consumed before this node.
-// SPEC: compile-time instance of the caller's configuration, as in epw_body (window_kernels.hip): 0 = everything from the argument block,
-// 1 = Lumina static tree + LANTERN + syntax shortcut + the Chameleon vocabulary constants, 4 = Anole static tree (neighbours zeroed in q).
+// SPEC: compile-time instance of the caller's configuration, as in epw_body (EpwSpecId, epw_config.h): EPW_SPEC_GENERIC = everything from the
+// argument block, EPW_SPEC_LUMINA_STATIC and EPW_SPEC_ANOLE_STATIC = the constants of kEpwSpec[SPEC] folded in.
 template <int NT, int E4, int IDMODE, bool FULLW, bool WIDE, int SPEC = 0>
 __device__ __forceinline__ void epn_node(const EpnArgs &args, const int b, const uint4 sw, const bool internal, const int ri, const int uoff,
                                          int &ph, int &tr_n, EpnVerdict &vd) {
@@ -86,17 +87,19 @@ __device__ __forceinline__ void epn_node(const EpnArgs &args, const int b, const
     extern __shared__ float4 dyn_lds[];
     float *g = reinterpret_cast<float *>(dyn_lds);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr bool SL = SPEC != 0;
-    const int W = SL ? 8192 : win.win_len, lo = SL ? 4 : win.win_lo, V = SL ? 65536 : prm.V;
+    constexpr EpwSpec CF = kEpwSpec[SPEC];          // what this instance assumes (epw_config.h; SPEC 0: nothing, everything from the argument block)
+    constexpr bool SL = SPEC != EPW_SPEC_GENERIC;
+    static_assert(!SL || (CF.mode != LANTERN_MODE_DYNAMIC && CF.lantern && CF.P == 0), "the node form's fixed configurations: static trees of any size, LANTERN on");
+    const int W = SL ? CF.win_len : win.win_len, lo = SL ? CF.win_lo : win.win_lo, V = SL ? CF.V : prm.V;
     uint32_t *nbmask = reinterpret_cast<uint32_t *>(g + W + EW_G_EXT);
     EnShared &S = *reinterpret_cast<EnShared *>(reinterpret_cast<char *>(g) + epn_shared_offset(W));
-    const int k = prm.k, off = SL ? 4 : prm.tok_offset;
-    const int p_mode = !SL ? prm.mode : (SPEC == 4 ? (int)LANTERN_MODE_STATIC_LG : (int)LANTERN_MODE_STATIC_LUMINA);
-    const bool p_lantern = SL ? true : prm.lantern != 0;
-    const bool p_syntax = SL ? SPEC == 1 : prm.syntax_shortcut != 0;
-    const int p_nsyn = SL ? (SPEC == 1 ? 4 : 0) : prm.n_syntax;
-    const int p_img_lo = SL ? 4 : prm.img_lo, p_img_hi = SL ? 8196 : prm.img_hi, p_trows = SL ? 8192 : prm.table_rows;
-    auto p_syn = [&](int q) -> int { return SL ? (q == 0 ? 8196 : (q == 1 ? 8197 : (q == 2 ? 8803 : 8828))) : prm.syntax[q]; };
+    const int k = prm.k, off = SL ? CF.tok_offset : prm.tok_offset;
+    const int p_mode = SL ? CF.mode : prm.mode;
+    const bool p_lantern = SL ? CF.lantern : prm.lantern != 0;
+    const bool p_syntax = SL ? CF.syntax_shortcut : prm.syntax_shortcut != 0;
+    const int p_nsyn = SL ? (CF.syntax_shortcut ? 4 : 0) : prm.n_syntax;
+    const int p_img_lo = SL ? CF.img_lo : prm.img_lo, p_img_hi = SL ? CF.img_hi : prm.img_hi, p_trows = SL ? CF.table_rows : prm.table_rows;
+    auto p_syn = [&](int q) -> int { return SL ? (q == 0 ? CF.syntax[0] : (q == 1 ? CF.syntax[1] : (q == 2 ? CF.syntax[2] : CF.syntax[3]))) : prm.syntax[q]; };
     const bool is_static = SL ? true : p_mode != LANTERN_MODE_DYNAMIC;
     const int nz = (k + 1 < prm.table_cols) ? k + 1 : prm.table_cols;
     const int32_t *tb = args.tables;
@@ -850,16 +853,13 @@ extern "C" int lantern_evaluate_posterior_nodes(const lantern_ep_params *prm, co
         else hipExtLaunchKernelGGL((epn_kernel<NT_, E4_, 1, FW_, true>), grid, dim3(NT_), lds, st, (hipEvent_t)ev0, nullptr, 0, args);                   \
         hipExtLaunchKernelGGL((epn_walk_kernel<NT_, E4_, FW_>), wgrid, dim3(NT_), wlds, st, nullptr, (hipEvent_t)ev1, 0, args);         \
     } while (0)
-    // compile-time instances for the reference's configurations on the Chameleon vocabulary (see epn_node): Lumina static (1), Anole static (4)
-    const int spec_knob = tuning(TUNE_EPW_SPEC);          // 0 = the generic instance
-    const bool chameleon = spec_knob != 0 && packed && !wide && W == 8192 && p.lantern && p.V == 65536 && p.img_lo == 4 && p.img_hi == 8196 && p.tok_offset == 4 &&
-                           p.table_rows == 8192 && win->win_lo == 4;
-    const bool lumina = chameleon && p.mode == LANTERN_MODE_STATIC_LUMINA && p.syntax_shortcut && p.n_syntax == 4 && p.syntax[0] == 8196 && p.syntax[1] == 8197 &&
-                        p.syntax[2] == 8803 && p.syntax[3] == 8828;
-    const bool anole = chameleon && p.mode == LANTERN_MODE_STATIC_LG && !p.syntax_shortcut;
+    // compile-time instances for the reference's static-tree configurations (see epn_node).  What this site adds to epw_spec_matches: the instances are built for
+    // the packed table and at most 4 children per node (packed && !wide); any number of rows per sequence is fine (nothing here stages row_hot in LDS).
+    const bool fixed = tuning(TUNE_EPW_SPEC) != 0 && packed && !wide;          // epw_spec = 0: the generic instance
+    const bool lumina = fixed && epw_spec_matches(EPW_SPEC_LUMINA_STATIC, p, *win), anole = fixed && epw_spec_matches(EPW_SPEC_ANOLE_STATIC, p, *win);
     if (lumina || anole) {
-        if (lumina) hipExtLaunchKernelGGL((epn_kernel<512, 4, 2, true, false, 1>), grid, dim3(512), lds, st, (hipEvent_t)ev0, nullptr, 0, args);
-        else hipExtLaunchKernelGGL((epn_kernel<512, 4, 2, true, false, 4>), grid, dim3(512), lds, st, (hipEvent_t)ev0, nullptr, 0, args);
+        if (lumina) hipExtLaunchKernelGGL((epn_kernel<512, 4, 2, true, false, EPW_SPEC_LUMINA_STATIC>), grid, dim3(512), lds, st, (hipEvent_t)ev0, nullptr, 0, args);
+        else hipExtLaunchKernelGGL((epn_kernel<512, 4, 2, true, false, EPW_SPEC_ANOLE_STATIC>), grid, dim3(512), lds, st, (hipEvent_t)ev0, nullptr, 0, args);
         hipExtLaunchKernelGGL((epn_walk_kernel<512, 4, true>), wgrid, dim3(512), wlds, st, nullptr, (hipEvent_t)ev1, 0, args);
     }
     else if (W == 8192) EPN_LAUNCH(512, 4, true);

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/lantern_hip.h"
+#include "tuning_slots.h"
 
 namespace lantern {
 void set_error(const char *fmt, ...);
@@ -39,13 +40,16 @@ void arm_launch_events(void *start, void *stop) {
 }
 
 // ---------------------------------------------------------------------------------------------- tuning values
-// (common.h `enum Tuning` names the same slots; this file does not include the HIP headers)
+// (tuning_slots.h lists the slots once: `enum Tuning` and this table come from the same list)
 namespace {
 struct TuningSlot { const char *name; int dflt; };
 const TuningSlot kTuning[] = {
-    {"epw_tp", 5}, {"epw_tp4", 1}, {"epw_tp_raw", 256}, {"epw_spec", 2}, {"epw_occ2", -1}, {"o7_nt", 0}, {"prep_nt", 0}, {"kv_u", 0}, {"kv_ks", 4},
-    {"kv_variant", 0}, {"gemm_tiled_from", 129}, {"sk_groups", 0}, {"sk_whole_mb", 40}, {"sk_nt_min_mb", 80}, {"ta_splits", 0}, {"ta_min_tiles", 2}, {"epw_tp_lg", 1}, {"epw_fused_helpers", 1}};
+#define LANTERN_TUNING_ROW(id, name, dflt) {name, dflt},
+    LANTERN_TUNING_SLOTS(LANTERN_TUNING_ROW)
+#undef LANTERN_TUNING_ROW
+};
 constexpr int kTuningCount = sizeof(kTuning) / sizeof(kTuning[0]);
+static_assert(kTuningCount == TUNE_COUNT, "one table row per enum Tuning slot");
 std::atomic<int> g_tuning[kTuningCount];
 std::atomic<bool> g_tuning_init{false};
 void tuning_init() {

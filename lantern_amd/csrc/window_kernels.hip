@@ -471,148 +471,205 @@ static int epw_check(const lantern_ep_params *prm, const lantern_ep_buffers *buf
     return LANTERN_OK;
 }
 
-static size_t epw_lds_bytes(const lantern_ep_params &p, const lantern_ep_window *win) {
-    const bool nucleus_logits = win->rows_kind == LANTERN_ROWS_LOGITS && p.top_p >= 1e-8f && p.top_p < 1.0f;      // top_p_tile's 256 f64 mass bins
-    return epw_shared_offset(win->win_len) + sizeof(EwShared) + (size_t)6 * epw_pd_cap(p.P, p.D) * 4 +
-           (win->rows_kind == LANTERN_ROWS_RAW_BF16 ? (size_t)O7_HIST_INTS * 4 : (nucleus_logits ? (size_t)256 * 8 : 0));
+// ---------------------------------------------------------------- which instance a launch gets (decides, launches nothing)
+// the latency instances (one workgroup per CU): raw rows with a nucleus filter; LlamaGen's 16384-id window on raw rows; the fixed configurations on the
+// packed 8192-id window, on raw rows and on probability rows; the chain launch that carries its prepare stage
+#define EPW_LATENCY_SPECS(RAW)                                                                                                                                 \
+    EPW_CHAIN(512, 4, 2, 1, true, RAW, EPW_SPEC_LUMINA_DEFAULT_TREE, 0) EPW_CHAIN(512, 4, 2, 1, true, RAW, EPW_SPEC_LUMINA_STATIC, 0)                          \
+    EPW_CHAIN(512, 4, 2, 1, true, RAW, EPW_SPEC_LUMINA_DYNAMIC, 0) EPW_CHAIN(512, 4, 2, 1, true, RAW, EPW_SPEC_ANOLE_STATIC, 0) EPW_CHAIN(512, 4, 2, 1, true, RAW, EPW_SPEC_GENERIC, 0)
+namespace lantern {
+EpwInstanceList epw_latency_instances() {
+    static const EpwInstance k[] = {
+        EPW_CHAIN(1024, 4, 1, 1, true, true, EPW_SPEC_GENERIC, EPW_NUCLEUS) EPW_CHAIN(512, 4, 2, 1, true, true, EPW_SPEC_GENERIC, EPW_NUCLEUS)
+        EPW_CHAIN(1024, 4, 1, 1, true, true, EPW_SPEC_LLAMAGEN_DYNAMIC, 0) EPW_CHAIN(1024, 4, 1, 1, true, true, EPW_SPEC_GENERIC, 0)
+        EPW_LATENCY_SPECS(true) EPW_LATENCY_SPECS(false)
+        EPW_FUSED_ENTRY(512, 4, 2, 1, true, true, EPW_SPEC_ANOLE_STATIC, 0) EPW_FUSED_ENTRY(512, 4, 2, 1, true, true, EPW_SPEC_LUMINA_DEFAULT_TREE, 0)
+        EPW_FUSED_ENTRY(512, 4, 2, 1, true, true, EPW_SPEC_LUMINA_STATIC, 0)
+    };
+    return {k, (int)(sizeof(k) / sizeof(k[0]))};
+}
+}  // namespace lantern
+
+// the tuning values the selection reads (lantern_tuning_set; meanings beside the slots in tuning_slots.h)
+struct EpwTuning {
+    int tp, tp4, tp_raw, spec, occ2, tp_lg;
+};
+static EpwTuning epw_tuning() {
+    return EpwTuning{tuning(TUNE_EPW_TP), tuning(TUNE_EPW_TP4), tuning(TUNE_EPW_TP_RAW), tuning(TUNE_EPW_SPEC), tuning(TUNE_EPW_OCC2), tuning(TUNE_EPW_TP_LG)};
+}
+struct EpwChoice {
+    EpwKey key;
+    size_t lds;
+};
+// how a candidate's neighbour ids are read: 0 from HBM on demand, 1 staged in LDS, 2 staged from the packed table with 16-byte loads
+static int epw_idmode(const lantern_ep_params &p, const lantern_ep_buffers &buf) {
+    const int nz = (p.k + 1 < p.table_cols) ? p.k + 1 : p.table_cols;
+    if (p.lantern && nz > EW_PF_K) return 0;
+    return (p.lantern && p.table_cols % 8 == 0 && ((uintptr_t)buf.nn_table & 15) == 0) ? 2 : 1;
+}
+
+// The instance for an argument block that passed epw_check, or false: no such instance.  `fused`: the chain launch that carries its prepare stage.
+static bool epw_select(const lantern_ep_params &p, const lantern_ep_buffers &buf, const lantern_ep_window &win, bool fused, const EpwTuning &t, EpwChoice *out) {
+    const int W = win.win_len, idmode = epw_idmode(p, buf);
+    const bool raw = win.rows_kind == LANTERN_ROWS_RAW_BF16, probs = win.rows_kind == LANTERN_ROWS_PROBS;
+    const bool nucleus = p.top_p >= 1e-8f && p.top_p < 1.0f;
+    const bool nucleus_logits = win.rows_kind == LANTERN_ROWS_LOGITS && nucleus;      // top_p_tile's 256 f64 mass bins
+    const size_t tables = (size_t)6 * epw_pd_cap(p.P, p.D) * 4;          // the per-(path, depth) tables behind the shared struct
+    size_t lds = epw_shared_offset(W) + sizeof(EwShared) + tables + (raw ? (size_t)O7_HIST_INTS * 4 : (nucleus_logits ? (size_t)256 * 8 : 0));
+    auto take = [&](int nt, int e4, int id, int wpe, bool fullw, bool rw, int spec, int tpo) {          // (the LDS bytes as they stand when the instance is taken)
+        *out = EpwChoice{EpwKey{fused, nt, e4, id, wpe, fullw, rw, spec, tpo}, lds};
+        return true;
+    };
+    // the argument-driven instances by window width, one workgroup per CU (epw_generic.hip)
+    auto generic = [&](int tpo) {
+        static const int tile[5][3] = {{1024, 256, 1}, {2048, 256, 2}, {4096, 512, 2}, {8192, 512, 4}, {16384, 1024, 4}};          // ids <=, threads, float4 per thread
+        for (const auto &g : tile)
+            if (W <= g[0]) return take(g[1], g[2], idmode, 1, false, false, EPW_SPEC_GENERIC, tpo);
+        return false;
+    };
+    // Every fixed-configuration instance keeps row_hot in LDS and takes final rows (probabilities, or raw rows it post-processes itself).
+    const bool fixed_ok = p.rows_per_seq <= EW_MAX_N && (raw || probs);
+    // one tree for all sequences / a tree per sequence: the static instances read no per-sequence sizes, the dynamic ones read them unconditionally
+    const bool one_tree = !buf.n_paths && !buf.n_depth && (!raw || !win.raw_pos_per_seq);
+    const bool per_seq_trees = buf.n_paths && buf.n_depth;
+    auto static_spec = [&](int spec_knob) {          // the fixed tree is picked by SIZES (P, D, N of mc_sim_7b_63) and stages at most 4 candidates per level ahead; a tree of the
+                                                     // same sizes with a wider fan-out still runs correctly (the restage path, tests: test_window_two_workgroups_per_cu_build[six_wide])
+        if (!fixed_ok || !one_tree) return (int)EPW_SPEC_GENERIC;
+        if (epw_spec_matches(EPW_SPEC_ANOLE_STATIC, p, win)) return (int)EPW_SPEC_ANOLE_STATIC;
+        if (!epw_spec_matches(EPW_SPEC_LUMINA_STATIC, p, win)) return (int)EPW_SPEC_GENERIC;
+        return (int)(spec_knob >= 2 && epw_spec_matches(EPW_SPEC_LUMINA_DEFAULT_TREE, p, win) ? EPW_SPEC_LUMINA_DEFAULT_TREE : EPW_SPEC_LUMINA_STATIC);
+    };
+    if (fused) {
+        // The static-tree latency instances on raw rows of the packed table, at most 256 sequences (one workgroup per CU besides the helpers).  A caller that asks for
+        // the fused form asks for a fixed-configuration instance -- there is no generic one -- so epw_spec = 0 does not apply here; epw_spec < 2 still turns the fixed tree off.
+        const int spec = static_spec(t.spec);
+        if (!raw || nucleus || idmode != 2 || p.B > 256 || spec == EPW_SPEC_GENERIC) return false;
+        return take(512, 4, 2, 1, true, true, spec, 0);
+    }
+    int spec = EPW_SPEC_GENERIC;          // epw_spec = 0: the generic instances everywhere
+    if (t.spec != 0) {
+        spec = static_spec(t.spec);
+        // (Lumina's dynamic raw rows carry per-sequence positions; LlamaGen has no grammar rows and reads none)
+        if (fixed_ok && per_seq_trees && (!raw || win.raw_pos_per_seq) && epw_spec_matches(EPW_SPEC_LUMINA_DYNAMIC, p, win)) spec = EPW_SPEC_LUMINA_DYNAMIC;
+        if (fixed_ok && per_seq_trees && epw_spec_matches(EPW_SPEC_LLAMAGEN_DYNAMIC, p, win)) spec = EPW_SPEC_LLAMAGEN_DYNAMIC;
+    }
+    const bool many = t.occ2 >= 0 ? t.occ2 != 0 : p.B > 256;          // more sequences than CUs: the throughput forms (epw_throughput.hip)
+    if (raw) {          // (epw_check: the 8192-id window on the packed table, or LlamaGen's 16384 ids)
+        if (nucleus) return W == 16384 ? take(1024, 4, 1, 1, true, true, EPW_SPEC_GENERIC, EPW_NUCLEUS) : take(512, 4, 2, 1, true, true, EPW_SPEC_GENERIC, EPW_NUCLEUS);
+        // LlamaGen's raw form: `spec` is LLAMAGEN_DYNAMIC or GENERIC here and nothing else, and epw_spec_matches decides it as a bare `V == 16384 && img_hi ==
+        // 16384 && tok_offset == 0 && per-sequence trees` would, ONLY because epw_check has pinned the rest for this form: LANTERN off, no grammar rows,
+        // dynamic mode, no syntax shortcut (its llamagen_form), and win_lo == img_lo, img_hi == win_lo + win_len for every raw launch.
+        if (W == 16384) return take(1024, 4, 1, 1, true, true, spec, 0);
+        if (many && t.tp >= 5 && spec != EPW_SPEC_GENERIC)
+            return t.tp_raw == 512 ? take(512, 4, 2, 4, true, true, spec, EPW_LATE_Q) : take(256, 8, 2, 2, true, true, spec, EPW_LATE_Q | EPW_ROTW);
+        return many ? take(512, 4, 2, 4, true, true, EPW_SPEC_GENERIC, 0) : take(512, 4, 2, 1, true, true, spec, 0);
+    }
+    if (nucleus) return generic(EPW_NUCLEUS);          // rows that arrive as logits, TopPLogitsWarper in the kernel
+    if (W > 4096 && W <= 8192) {
+        const bool packed_window = W == 8192 && idmode == 2;          // the Lumina / Anole image window on the packed table
+        if (many && !packed_window) return take(512, 4, idmode, 4, false, false, EPW_SPEC_GENERIC, 0);
+        if (!packed_window) return generic(0);
+        if (!many) return take(512, 4, 2, 1, true, false, spec, 0);
+        // Throughput form of the fixed-configuration instances (the shape BASELINE's roofline target is assessed on): 256 threads x 8 float4 per thread, three
+        // workgroups per CU (53 KB of LDS each, <= 168 VGPRs at 3 waves per SIMD), drafter rows requested only once a rejection is known.  At saturation
+        // the kernel is bound by instruction ISSUE (profiles/r04_ep_sweep_pmc.txt), so half the waves per sequence is what pays: 4096 sequences per
+        // launch 293 us (generic, 512 threads, two per CU) -> 228 (fixed configuration, 512 threads) -> 194 (owner-wave sibling zeroing) -> 163 us.
+        if (t.tp >= 5 && spec == EPW_SPEC_LUMINA_DEFAULT_TREE && t.tp4 != 0) {          // the compact four-per-CU forms: their own (smaller) LDS block
+            lds = epw_shared_offset(8192, false) + sizeof(EwSharedCompact) + tables;
+            const int tpo = EPW_LATE_Q | EPW_COMPACT | (t.tp4 == 2 ? 0 : (t.tp4 == 3 ? EPW_ALLW | EPW_LDS2P : (t.tp4 == 4 ? EPW_ROTW | EPW_LDS2P : EPW_ROTW | EPW_LDS2P | EPW_PRIO)));
+            return take(256, 8, 2, 4, true, false, spec, tpo);
+        }
+        if (t.tp >= 5 && spec != EPW_SPEC_GENERIC) return take(256, 8, 2, 3, true, false, spec, EPW_LATE_Q | EPW_ROTW);
+        // epw_tp < 5 (diagnostic): the 512-thread forms, two per CU -- 0: the generic instance; 1..4: the default tree's fixed-configuration instance
+        return take(512, 4, 2, 4, true, false, (spec == EPW_SPEC_LUMINA_DEFAULT_TREE && t.tp >= 1) ? spec : (int)EPW_SPEC_GENERIC, 0);
+    }
+    // LlamaGen's standard verify at more sequences than CUs: two workgroups per CU on the small staged tables, if tree and tables fit them
+    const size_t lds_lite = epw_shared_offset(W, false) + sizeof(EwSharedLite) + tables;
+    if (many && t.tp_lg != 0 && spec == EPW_SPEC_LLAMAGEN_DYNAMIC && probs && p.rows_per_seq <= EwSharedLite::kMaxN && lds_lite <= (size_t)80 * 1024) {
+        lds = lds_lite;
+        const int tpo = EPW_LATE_Q | EPW_ROTW | EPW_LITE | (t.tp_lg == 2 ? EPW_LDS2P : (t.tp_lg == 3 ? 0 : (t.tp_lg == 4 ? EPW_PRIO | EPW_DMAROW : EPW_DMAROW)));
+        return take(512, 8, 1, 4, true, false, spec, tpo);
+    }
+    return generic(0);
+}
+
+static const EpwInstance *epw_find(const EpwKey &k) {
+    for (const EpwInstanceList &l : {epw_latency_instances(), epw_generic_instances(), epw_throughput_instances()})
+        for (int i = 0; i < l.n; ++i)
+            if (!memcmp(&l.v[i].key, &k, sizeof(EpwKey))) return &l.v[i];          // (nine ints: no padding)
+    return nullptr;
+}
+
+static int fused_refused() {
+    set_error("fused prepare: Lumina or Anole static trees on raw bf16 rows (8192-id window, packed table, k + 1 <= %d, top_p off), at most 256 sequences, a node list "
+              "whose rows go to ep_win.raw_probs, and the row_ready words", EW_PF_K);
+    return LANTERN_E_UNSUPPORTED;
+}
+
+// epw_check + epw_select + epw_find with a launch's status codes and messages; *inst stays null for an empty batch
+static int epw_instance(const lantern_ep_params *prm, const lantern_ep_buffers *buf, const lantern_ep_window *win, bool fused, EpwChoice *c, const EpwInstance **inst) {
+    *inst = nullptr;
+    const int rc = epw_check(prm, buf, win);
+    if (rc || prm->B == 0) return rc;
+    if (!epw_select(*prm, *buf, *win, fused, epw_tuning(), c)) {
+        if (fused) return fused_refused();
+        set_error("evaluate_posterior_window: no kernel instance for window %d, id mode %d%s", win->win_len, epw_idmode(*prm, *buf),
+                  (prm->top_p >= 1e-8f && prm->top_p < 1.0f) ? ", top_p inside the kernel" : "");
+        return LANTERN_E_UNSUPPORTED;
+    }
+    *inst = epw_find(c->key);
+    if (!*inst) {          // (a defect of the instance lists, not of the caller's arguments: tests/test_epw_select_cpu.py walks every reachable key)
+        set_error("evaluate_posterior_window: the selected instance is not in the library's instance lists");
+        return LANTERN_E_LAUNCH;
+    }
+    return LANTERN_OK;
+}
+
+extern "C" int lantern_evaluate_posterior_window_instance(const lantern_ep_params *prm, const lantern_ep_buffers *buf, const lantern_ep_window *win, int fused,
+                                                          char *name, int cap) {
+    LANTERN_CHECK_ARG(name && cap > 0, "evaluate_posterior_window_instance: no room for the name");
+    name[0] = 0;
+    EpwChoice c;
+    const EpwInstance *inst;
+    const int rc = epw_instance(prm, buf, win, fused != 0, &c, &inst);
+    if (rc || !inst) return rc;
+    const EpwKey &k = c.key;
+    const int n = snprintf(name, (size_t)cap, "%s<%d,%d,%d,%d,%s,%s,%d,%d>", k.fused ? "epw_kernel_fused" : "epw_kernel", k.nt, k.e4, k.idmode, k.wpe, k.fullw ? "true" : "false",
+                           k.raw ? "true" : "false", k.spec, k.tpo);
+    LANTERN_CHECK_ARG(n > 0 && n < cap, "evaluate_posterior_window_instance: the name needs %d bytes", n + 1);
+    return LANTERN_OK;
 }
 
 extern "C" int lantern_evaluate_posterior_window(const lantern_ep_params *prm, const lantern_ep_buffers *buf,
                                                  const lantern_ep_window *win, void *stream) {
-    const int rc = epw_check(prm, buf, win);
-    if (rc) return rc;
-    const lantern_ep_params &p = *prm;
-    if (p.B == 0) return LANTERN_OK;
-    const bool raw = win->rows_kind == LANTERN_ROWS_RAW_BF16;
-    hipStream_t st = (hipStream_t)stream;
-    const int W = win->win_len;
-    const size_t lds = epw_lds_bytes(p, win);
-    dim3 grid(p.B);
-    const int nz = (p.k + 1 < p.table_cols) ? p.k + 1 : p.table_cols;
-    const bool lds_ids = !p.lantern || nz <= EW_PF_K;
-    const EpwArgs args{p, *buf, *win};
-    const int idmode = !lds_ids ? 0 : ((p.lantern && p.table_cols % 8 == 0 && ((uintptr_t)buf->nn_table & 15) == 0) ? 2 : 1);
-    const EpwLaunch L{grid, lds, st};
-    // the headline shape gets its own instance (SPEC 1: mode / LANTERN / syntax-shortcut flags are compile-time constants there)
-    const int spec_knob = tuning(TUNE_EPW_SPEC);          // 0 = the generic instance, 1 = no fixed tree
-    const bool chameleon = spec_knob != 0 && p.lantern && p.V == 65536 && p.img_lo == 4 && p.img_hi == 8196 && p.tok_offset == 4 && p.table_rows == 8192 &&
-                           win->win_lo == 4 && W == 8192 && p.rows_per_seq <= EW_MAX_N && (raw || win->rows_kind == LANTERN_ROWS_PROBS) &&
-                           (!raw || win->raw_w_latent == 0 || (win->raw_eos_id == 8196 && win->raw_newline_id == 8803));
-    const bool lumina_syntax = p.syntax_shortcut && p.n_syntax == 4 && p.syntax[0] == 8196 && p.syntax[1] == 8197 && p.syntax[2] == 8803 && p.syntax[3] == 8828;
-    const bool lumina_static = chameleon && p.mode == LANTERN_MODE_STATIC_LUMINA && lumina_syntax && !buf->n_paths && !buf->n_depth && (!raw || !win->raw_pos_per_seq);
-    const bool lumina_dynamic = chameleon && p.mode == LANTERN_MODE_DYNAMIC && lumina_syntax && buf->n_paths && buf->n_depth && (!raw || win->raw_pos_per_seq);
-    const bool anole_static = chameleon && p.mode == LANTERN_MODE_STATIC_LG && !p.syntax_shortcut && !buf->n_paths && !buf->n_depth &&
-                              (!raw || (win->raw_w_latent == 0 && !win->raw_pos_per_seq));
-    // the fixed-tree instance is picked by SIZES (P, D, N of mc_sim_7b_63) and stages at most 4 candidates per level ahead; a tree of the same sizes
-    // with a wider fan-out still runs correctly (the restage path, tests: test_window_two_workgroups_per_cu_build[six_wide])
-    const bool default_tree = spec_knob >= 2 && p.P == 15 && p.D == 6 && p.N == 26 && p.rows_per_seq == 26;
-    const int occ_knob = tuning(TUNE_EPW_OCC2);
-    const bool many = occ_knob >= 0 ? occ_knob != 0 : p.B > 256;          // more sequences than CUs: the throughput forms (epw_throughput.hip)
-    // Throughput form of the fixed-configuration instances (the shape BASELINE's roofline target is assessed on): 256 threads x 8 float4 per thread, three
-    // workgroups per CU (53 KB of LDS each, <= 168 VGPRs at 3 waves per SIMD), drafter rows requested only once a rejection is known.  At saturation
-    // the kernel is bound by instruction ISSUE (profiles/r04_ep_sweep_pmc.txt), so half the waves per sequence is what pays: 4096 sequences per
-    // launch 293 us (generic, 512 threads, two per CU) -> 228 (fixed configuration, 512 threads) -> 194 (owner-wave sibling zeroing) -> 163 us.
-    // LANTERN_EPW_TP=0: the generic two-per-CU instance; 1: the 512-thread fixed-configuration instance (diagnostic).
-    const int tp_knob = tuning(TUNE_EPW_TP);
-    const bool nucleus = p.top_p >= 1e-8f && p.top_p < 1.0f;
-    bool ok = true;
-    if (raw && nucleus) {          // raw rows with a nucleus filter: the generic raw instances with the filter compiled in
-        if (W == 16384) LANTERN_LAUNCH((epw_kernel<1024, 4, 1, 1, true, true, 0, 2>), grid, dim3(1024), lds, st, args);
-        else LANTERN_LAUNCH((epw_kernel<512, 4, 2, 1, true, true, 0, 2>), grid, dim3(512), lds, st, args);
-    }
-    else if (raw && W == 16384) {          // LlamaGen standard verify on raw rows (the form epw_check admitted)
-        const bool lg_dynamic = spec_knob != 0 && p.V == 16384 && p.img_lo == 0 && p.img_hi == 16384 && p.tok_offset == 0 && win->win_lo == 0 && buf->n_paths &&
-                                buf->n_depth && p.rows_per_seq <= EW_MAX_N;
-        if (lg_dynamic) LANTERN_LAUNCH((epw_kernel<1024, 4, 1, 1, true, true, 5>), grid, dim3(1024), lds, st, args);
-        else LANTERN_LAUNCH((epw_kernel<1024, 4, 1, 1, true, true>), grid, dim3(1024), lds, st, args);
-    }
-    else if (raw) {
-        const bool tp_raw = many && tp_knob >= 5;
-        if (tp_raw && lumina_static && default_tree) ok = epw_launch_throughput(EPW_TP_RAW_LUMINA_DEFAULT_TREE, L, args);
-        else if (tp_raw && lumina_static) ok = epw_launch_throughput(EPW_TP_RAW_LUMINA_STATIC, L, args);
-        else if (tp_raw && lumina_dynamic) ok = epw_launch_throughput(EPW_TP_RAW_LUMINA_DYNAMIC, L, args);
-        else if (tp_raw && anole_static) ok = epw_launch_throughput(EPW_TP_RAW_ANOLE_STATIC, L, args);
-        else if (many) ok = epw_launch_throughput(EPW_TP_RAW_GENERIC, L, args);
-        else if (lumina_static && default_tree) LANTERN_LAUNCH((epw_kernel<512, 4, 2, 1, true, true, 2>), grid, dim3(512), lds, st, args);
-        else if (lumina_static) LANTERN_LAUNCH((epw_kernel<512, 4, 2, 1, true, true, 1>), grid, dim3(512), lds, st, args);
-        else if (lumina_dynamic) LANTERN_LAUNCH((epw_kernel<512, 4, 2, 1, true, true, 3>), grid, dim3(512), lds, st, args);
-        else if (anole_static) LANTERN_LAUNCH((epw_kernel<512, 4, 2, 1, true, true, 4>), grid, dim3(512), lds, st, args);
-        else LANTERN_LAUNCH((epw_kernel<512, 4, 2, 1, true, true>), grid, dim3(512), lds, st, args);
-    }
-    else if (nucleus) ok = epw_launch_generic(W, idmode, true, L, args);          // rows that arrive as logits, TopPLogitsWarper in the kernel
-    else if (W > 4096 && W <= 8192) {
-        const bool tp_form = many && W == 8192 && idmode == 2 && tp_knob >= 5;
-        if (tp_form && lumina_static && default_tree) ok = epw_launch_throughput(EPW_TP_LUMINA_DEFAULT_TREE, L, args);
-        else if (tp_form && lumina_static) ok = epw_launch_throughput(EPW_TP_LUMINA_STATIC, L, args);
-        else if (tp_form && lumina_dynamic) ok = epw_launch_throughput(EPW_TP_LUMINA_DYNAMIC, L, args);
-        else if (tp_form && anole_static) ok = epw_launch_throughput(EPW_TP_ANOLE_STATIC, L, args);
-        else if (many && W == 8192 && idmode == 2 && lumina_static && default_tree && tp_knob >= 1) ok = epw_launch_throughput(EPW_TP_512_DEFAULT_TREE, L, args);
-        else if (many && W == 8192 && idmode == 2) ok = epw_launch_throughput(EPW_TP_512_PACKED, L, args);
-        else if (many) ok = epw_launch_throughput(idmode == 2 ? EPW_TP_512_ID2 : (idmode == 1 ? EPW_TP_512_ID1 : EPW_TP_512_ID0), L, args);
-        else if (W == 8192 && idmode == 2) {
-            if (lumina_static && default_tree) LANTERN_LAUNCH((epw_kernel<512, 4, 2, 1, true, false, 2>), grid, dim3(512), lds, st, args);
-            else if (lumina_static) LANTERN_LAUNCH((epw_kernel<512, 4, 2, 1, true, false, 1>), grid, dim3(512), lds, st, args);
-            else if (lumina_dynamic) LANTERN_LAUNCH((epw_kernel<512, 4, 2, 1, true, false, 3>), grid, dim3(512), lds, st, args);
-            else if (anole_static) LANTERN_LAUNCH((epw_kernel<512, 4, 2, 1, true, false, 4>), grid, dim3(512), lds, st, args);
-            else LANTERN_LAUNCH((epw_kernel<512, 4, 2, 1, true>), grid, dim3(512), lds, st, args);   // the Lumina / Anole image window on the packed table
-        }
-        else ok = epw_launch_generic(W, idmode, false, L, args);
-    }
-    else if (W == 16384 && many && tuning(TUNE_EPW_TP_LG) != 0 && spec_knob != 0 && !p.lantern && p.mode == LANTERN_MODE_DYNAMIC && !p.syntax_shortcut && p.V == 16384 &&
-             p.img_lo == 0 && p.img_hi >= 16384 && p.tok_offset == 0 && win->win_lo == 0 && buf->n_paths && buf->n_depth && win->rows_kind == LANTERN_ROWS_PROBS &&
-             p.rows_per_seq <= EwSharedLite::kMaxN &&
-             epw_shared_offset(W, false) + sizeof(EwSharedLite) + (size_t)6 * epw_pd_cap(p.P, p.D) * 4 <= (size_t)80 * 1024) {
-        // LlamaGen's standard verify at more sequences than CUs: two workgroups per CU (epw_throughput.hip)
-        const EpwLaunch Llg{grid, epw_shared_offset(W, false) + sizeof(EwSharedLite) + (size_t)6 * epw_pd_cap(p.P, p.D) * 4, st};
-        ok = epw_launch_throughput(EPW_TP_LLAMAGEN_DYNAMIC, Llg, args);
-    }
-    else ok = epw_launch_generic(W, idmode, false, L, args);
-    if (!ok) {
-        set_error("evaluate_posterior_window: no kernel instance for window %d, id mode %d%s", W, idmode, nucleus ? ", top_p inside the kernel" : "");
-        return LANTERN_E_UNSUPPORTED;
-    }
+    EpwChoice c;
+    const EpwInstance *inst;
+    const int rc = epw_instance(prm, buf, win, false, &c, &inst);
+    if (rc || !inst) return rc;
+    inst->launch(EpwLaunch{dim3(prm->B), c.lds, (hipStream_t)stream}, EpwArgs{*prm, *buf, *win}, nullptr);
     LANTERN_CHECK_LAUNCH("evaluate_posterior_window");
     return LANTERN_OK;
 }
 
-// The chain launch with its prepare stage inside (lantern_step_group flags & LANTERN_STEP_FUSED_PREPARE, verify_step.cpp): the static-tree latency instances (Lumina,
-// Anole) on raw rows, at most 256 sequences.  Anything else is refused -- the caller asked for a form that does not exist, it is not quietly run in three launches.
+// The chain launch with its prepare stage inside (lantern_step_group flags & LANTERN_STEP_FUSED_PREPARE, verify_step.cpp).  Anything the selection has no fused
+// instance for is refused -- the caller asked for a form that does not exist, it is not quietly run in three launches.
 namespace lantern {
 int evaluate_posterior_window_fused(const lantern_ep_params *prm, const lantern_ep_buffers *buf, const lantern_ep_window *win, const PrepArgs &prep, int32_t *ready,
                                     int32_t epoch, void *stream) {
-    const int rc = epw_check(prm, buf, win);
-    if (rc) return rc;
+    EpwChoice c;
+    const EpwInstance *inst;
+    const int rc = epw_instance(prm, buf, win, true, &c, &inst);
+    if (rc || !inst) return rc;
     const lantern_ep_params &p = *prm;
-    if (p.B == 0) return LANTERN_OK;
-    const int W = win->win_len;
-    const bool raw = win->rows_kind == LANTERN_ROWS_RAW_BF16;
-    const bool nucleus = p.top_p >= 1e-8f && p.top_p < 1.0f;
-    const bool lumina_syntax = p.syntax_shortcut && p.n_syntax == 4 && p.syntax[0] == 8196 && p.syntax[1] == 8197 && p.syntax[2] == 8803 && p.syntax[3] == 8828;
-    // the Chameleon image window on the packed table, one tree for all sequences (the conditions under which lantern_evaluate_posterior_window takes a SPEC instance)
-    const bool chameleon = raw && !nucleus && p.lantern && p.V == 65536 && p.img_lo == 4 && p.img_hi == 8196 && p.tok_offset == 4 && p.table_rows == 8192 && win->win_lo == 4 &&
-                           W == 8192 && p.rows_per_seq <= EW_MAX_N && !buf->n_paths && !buf->n_depth && !win->raw_pos_per_seq && p.table_cols % 8 == 0 &&
-                           ((uintptr_t)buf->nn_table & 15) == 0 && ((p.k + 1 < p.table_cols ? p.k + 1 : p.table_cols) <= EW_PF_K) && p.B <= 256;
-    const bool lumina = chameleon && p.mode == LANTERN_MODE_STATIC_LUMINA && lumina_syntax && (win->raw_w_latent == 0 || (win->raw_eos_id == 8196 && win->raw_newline_id == 8803));
-    const bool anole = chameleon && p.mode == LANTERN_MODE_STATIC_LG && !p.syntax_shortcut && win->raw_w_latent == 0;
-    const bool form = lumina || anole;
-    if (!form || !ready || !win->raw_probs || !win->raw_pre || prep.n_list < 1 || prep.B != p.B || prep.PD != p.P * p.D || prep.N != p.N || prep.rows_per_seq != p.rows_per_seq ||
-        prep.out_win != win->raw_probs || prep.W != W || !prep.cand || !prep.tree_cand || (prep.top_p >= 1e-8f && prep.top_p < 1.0f)) {
-        set_error("fused prepare: Lumina or Anole static trees on raw bf16 rows (8192-id window, packed table, k + 1 <= %d, top_p off), at most 256 sequences, a node list "
-                  "whose rows go to ep_win.raw_probs, and the row_ready words", EW_PF_K);
-        return LANTERN_E_UNSUPPORTED;
-    }
-    const size_t lds = epw_lds_bytes(p, win);
-    const EpwArgs args{p, *buf, *win};
+    // the prepare stage's own arguments: the node list's rows go where the chain reads them
+    if (!ready || !win->raw_probs || !win->raw_pre || prep.n_list < 1 || prep.B != p.B || prep.PD != p.P * p.D || prep.N != p.N || prep.rows_per_seq != p.rows_per_seq ||
+        prep.out_win != win->raw_probs || prep.W != win->win_len || !prep.cand || !prep.tree_cand || (prep.top_p >= 1e-8f && prep.top_p < 1.0f))
+        return fused_refused();
     int per = tuning(TUNE_EPW_FUSED_HELPERS);          // helper workgroups per sequence (each takes its listed rows one after the other)
     if (per < 1) per = 1;
     if (per > prep.n_list - 1) per = prep.n_list - 1;          // (a list of the root alone: no helper, the sequences post-process every row themselves)
     const EpwFused fz{prep, ready, epoch, p.B * per};
-    const dim3 grid(fz.n_helpers + p.B);
-    const bool default_tree = tuning(TUNE_EPW_SPEC) >= 2 && p.P == 15 && p.D == 6 && p.N == 26 && p.rows_per_seq == 26;
-    hipStream_t st = (hipStream_t)stream;
-    if (anole) LANTERN_LAUNCH((epw_kernel_fused<512, 4, 2, 1, true, true, 4, 0>), grid, dim3(512), lds, st, args, fz);
-    else if (default_tree) LANTERN_LAUNCH((epw_kernel_fused<512, 4, 2, 1, true, true, 2, 0>), grid, dim3(512), lds, st, args, fz);
-    else LANTERN_LAUNCH((epw_kernel_fused<512, 4, 2, 1, true, true, 1, 0>), grid, dim3(512), lds, st, args, fz);
+    inst->launch(EpwLaunch{dim3(fz.n_helpers + p.B), c.lds, (hipStream_t)stream}, EpwArgs{p, *buf, *win}, &fz);
     LANTERN_CHECK_LAUNCH("evaluate_posterior_window (fused prepare)");
     return LANTERN_OK;
 }

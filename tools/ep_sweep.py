@@ -1,6 +1,6 @@
 """evaluate_posterior alone at given batch sizes, on ROTATING inputs (bench.py's ep_batch_sweep, stand-alone): the target of the
 rocprofv3 --kernel-trace --stats / --pmc passes at the saturating batch (tools/run/ep_sweep_prof.sh) and of tuning runs
-(LANTERN_EPW_TP / LANTERN_EPW_OCC2 select the kernel instance).
+(LANTERN_EPW_TP / LANTERN_EPW_OCC2 in this tool's environment become lantern_tuning_set calls and select the kernel instance).
 
 usage: ep_sweep.py <batches, e.g. 512,4096> [iters] [kernels, e.g. chain or chain,nodes]"""
 import json
@@ -23,4 +23,4 @@ dev = torch.device("cuda", 0)
 torch.cuda.set_device(dev)
 base = HN.WorkloadConfig()
 res = bench.ep_batch_sweep(batches, dev, base, iters=iters, kernels=kernels)
-print(json.dumps({"knobs": {k: os.environ.get(k) for k in ("LANTERN_EPW_TP", "LANTERN_EPW_OCC2", "LANTERN_EPW_SPEC")}, "sweep": res}))
+print(json.dumps({"knobs": _KNOBS, "sweep": res}))          # (the tuning values really applied, not what the environment says)

@@ -1,6 +1,6 @@
 """evaluate_posterior on RAW cond / uncond bf16 rows (LANTERN_ROWS_RAW_BF16: the row post-process of the visited rows inside the chain kernel) at
-batch sizes beyond the CU count -- the throughput instances of epw_throughput.hip (LANTERN_EPW_TP_RAW=512 selects the 512-thread form,
-LANTERN_EPW_TP=0 the generic two-per-CU instance).  Kernel-only durations from the launch's own HIP events.
+batch sizes beyond the CU count -- the throughput instances of epw_throughput.hip (in this tool's environment, applied as lantern_tuning_set calls:
+LANTERN_EPW_TP_RAW=512 selects the 512-thread form, LANTERN_EPW_TP=0 the generic two-per-CU instance).  Kernel-only durations from the launch's own HIP events.
 usage: raw_sweep.py <batches, e.g. 512,2048> [steps] [spec_rows]"""
 import json
 import os
@@ -43,4 +43,4 @@ for B in batches:
                 "per_step": {k: float(cnt[..., j].float().mean()) for j, k in enumerate(("levels", "tried", "rejected"))}})
     del wl
     torch.cuda.empty_cache()
-print(json.dumps({"knobs": {k: os.environ.get(k) for k in ("LANTERN_EPW_TP", "LANTERN_EPW_TP_RAW", "LANTERN_EPW_SPEC")}, "raw_sweep": out}))
+print(json.dumps({"knobs": _KNOBS, "raw_sweep": out}))
