@@ -681,14 +681,32 @@ int lantern_pack_linear_weight(const void *W, int n_rows, int K, int pair_rows, 
  * (q_out [N, K] uint8 row-major, scale_out [N] f32, N = n_rows or 2 * pair_rows as for the source weight).  lantern_pack_linear_weight_fp8 quantises
  * and packs on the device (one pass for the row maxima, one for the bricks); W [dev] bf16 row-major, out [dev]
  * lantern_pack_linear_weight_fp8_bytes(n_rows, K, pair_rows) bytes, 16-byte aligned.  A combination without a kernel -- LANTERN_PACKED_FP8 with
- * K % 64 != 0 -- returns LANTERN_E_UNSUPPORTED with a message; the per-tile entry points (lantern_linear_rows, _epilogue, _splitk, _packed,
- * lantern_drafter_fc, lantern_head_expand) have no `packed` argument and read bf16 only: nothing falls back silently. */
+ * K % 64 != 0 -- returns LANTERN_E_UNSUPPORTED with a message; the entry points without a `packed` argument (lantern_linear_rows, _epilogue, _splitk,
+ * _packed, lantern_drafter_fc, lantern_head_expand) read bf16 only: nothing falls back silently.  Above the drafting shape (the prompt prefill) an FP8
+ * weight is read by the two `_fmt` / `_packed` entries declared below, which take the format as an argument. */
 #define LANTERN_PACKED_BF16 1
 #define LANTERN_PACKED_FP8 2
 size_t lantern_pack_linear_weight_fp8_bytes(int n_rows, int K, int pair_rows);
 int lantern_pack_linear_weight_fp8(const void *W, int n_rows, int K, int pair_rows, void *out, void *stream);
 int lantern_unpack_linear_weight_fp8(const void *packed, int n_rows, int K, int pair_rows, uint8_t *q_out /* [N, K] */, float *scale_out /* [N] */,
                                      void *stream);
+/* lantern_linear_rows_packed with the packed weight's format as an argument (the prompt prefill of a drafter whose weights are FP8):
+ *   packed = LANTERN_PACKED_BF16: lantern_linear_rows_packed itself, same kernels, same bits;
+ *   packed = LANTERN_PACKED_FP8: the LDS-tiled GEMM (128 rows x 128 columns per workgroup) on the FP8 bricks for ANY M >= 1 -- the codes are expanded to
+ *     bf16 exactly and contracted by the bf16 tiled kernel's MFMA sequence, the finished f32 sum is multiplied by the row's scale before the bias (a
+ *     gate / up pair: each its own scale), every later rounding as in the bf16 kernel.  The "gemm_tiled_from" tuning value chooses between the two
+ *     bf16 kernels only: there is no FP8 row-blocked kernel and nothing falls back to another format or kernel;
+ *   any other value (0 included): LANTERN_E_INVALID -- these two entries take exactly the two codes, so that a later format is never read as bf16.
+ * Every other argument, and every argument check (all on the host, before anything is launched), as for lantern_linear_rows_packed. */
+int lantern_linear_rows_packed_fmt(const void *A, const void *W_packed, const void *bias, int M, int K, int n_rows, void *out, int out_stride,
+                                   int epilogue, const void *aux, int aux_stride, int pair_rows, int packed, void *stream);
+/* O11, out = bf16(fc(cat(embed[ids] * embed_scale, hidden)) + bias), at prefill row counts (ANY M) on the PACKED [H, 2H] weight of either format
+ * (lantern_pack_linear_weight / _fp8 with n_rows = H, K = 2H, pair_rows = 0; packed = LANTERN_PACKED_BF16 or LANTERN_PACKED_FP8, anything else: LANTERN_E_INVALID):
+ * the same tiled GEMM with the embedding gather, its scaling (re-rounded to bf16, only for embed_scale > 1; ids clamped to [0, vocab)) and the concat folded
+ * into the A-tile loads, as the stream-K form folds them into its A fragments.  H % 64 == 0.  ids [dev] int64 [M], hidden [dev] bf16 [M, H], embed [dev]
+ * bf16 [vocab, H], bias [dev] bf16 [H] or NULL, out [dev] bf16 [M, H]. */
+int lantern_drafter_fc_packed(const int64_t *ids, const void *hidden, const void *embed, const void *W_packed, const void *bias, int M, int H, int vocab,
+                              float embed_scale, void *out, int packed, void *stream);
 int lantern_rmsnorm_rows(const void *x, const void *weight, int M, int H, float eps, void *out, void *stream);
 int lantern_qk_norm_rope(const void *qkv, int B, int T, int n_q_heads, int n_kv_heads, int head_dim, const void *q_weight, const void *q_bias,
                          const void *k_weight, const void *k_bias, int model_parallel, const void *cos_table, const void *sin_table,

@@ -60,6 +60,18 @@ __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
     return (uint16_t)(u >> 16);
 }
 
+// eight bf16 values times an f32 scale, each product rounded to bf16 again (`inputs_embeds * embed_upscale` in bf16, cnets_lumina_mgpt.py:1096-1097)
+__device__ __forceinline__ uint4 scale_bf16x8(uint4 v, float scale) {
+    uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint16_t lo = f32_to_bf16_rne(bf16_bits_to_f32((uint16_t)(w[i] & 0xffffu)) * scale);
+        const uint16_t hi = f32_to_bf16_rne(bf16_bits_to_f32((uint16_t)(w[i] >> 16)) * scale);
+        w[i] = (uint32_t)lo | ((uint32_t)hi << 16);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // COLS = output columns per workgroup: 32 fills the 32x32 MFMA tile; 16 (half of the tile's columns idle -- the matrix
 // cores are nowhere near the limit of this weight-streaming kernel) doubles the workgroup count when H / 32 would leave
 // CUs without work (H = 4096: 128 -> 256 workgroups).
@@ -105,17 +117,7 @@ __global__ __launch_bounds__(FC_THREADS) void drafter_fc_kernel(const int64_t *_
         if (!live[mt]) return zero;
         if (k0 >= H) return load_frag(hrow[mt] + (k0 - H));
         bf16x8_t afrag = load_frag(erow[mt] + k0);
-        if (embed_scale > 1.0f) {   // inputs_embeds * embed_upscale, rounded to bf16 (cnets_lumina_mgpt.py:1096-1097)
-            uint4 v = __builtin_bit_cast(uint4, afrag);
-            uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint16_t lo = f32_to_bf16_rne(bf16_bits_to_f32((uint16_t)(w[i] & 0xffffu)) * embed_scale);
-                const uint16_t hi = f32_to_bf16_rne(bf16_bits_to_f32((uint16_t)(w[i] >> 16)) * embed_scale);
-                w[i] = (uint32_t)lo | ((uint32_t)hi << 16);
-            }
-            afrag = __builtin_bit_cast(bf16x8_t, make_uint4(w[0], w[1], w[2], w[3]));
-        }
+        if (embed_scale > 1.0f) afrag = __builtin_bit_cast(bf16x8_t, scale_bf16x8(__builtin_bit_cast(uint4, afrag), embed_scale));
         return afrag;
     };
     // four K steps per trip with the k order permuted so that a lane streams 64 contiguous bytes of its weight row (see
@@ -826,17 +828,7 @@ __global__ __launch_bounds__(FC_THREADS) void linear_rows_streamk_kernel(const S
         } else {
             if (k0 >= a.hsplit) return load_frag(arow + (k0 - a.hsplit));
             bf16x8_t af = load_frag(erow + k0);
-            if (a.embed_scale > 1.0f) {
-                const uint4 v = __builtin_bit_cast(uint4, af);
-                uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const uint16_t lo = f32_to_bf16_rne(bf16_bits_to_f32((uint16_t)(w[i] & 0xffffu)) * a.embed_scale);
-                    const uint16_t hi = f32_to_bf16_rne(bf16_bits_to_f32((uint16_t)(w[i] >> 16)) * a.embed_scale);
-                    w[i] = (uint32_t)lo | ((uint32_t)hi << 16);
-                }
-                af = __builtin_bit_cast(bf16x8_t, make_uint4(w[0], w[1], w[2], w[3]));
-            }
+            if (a.embed_scale > 1.0f) af = __builtin_bit_cast(bf16x8_t, scale_bf16x8(__builtin_bit_cast(uint4, af), a.embed_scale));
             return af;
         }
     };
@@ -1142,13 +1134,29 @@ __global__ __launch_bounds__(FC_THREADS) void linear_rows_packed_kernel(const ui
 // global loads in flight under this block's MFMAs; the weights come straight from the packed bricks (already in B-fragment order: 16 bytes
 // per lane and MFMA step, no LDS), next block's prefetched into a second register set.  The row-blocked kernel above (kept for 33 - 128 rows) re-reads A from L2 for
 // every 32-column tile (15 GB at 1200 rows of the 7B layer); here A crosses L2 -> LDS once per 128 columns.
+//  * W8: Wp is the output of lantern_pack_linear_weight_fp8 -- the same brick sequence at one byte per element (2 KB per brick, [half j][lane][16 bytes]:
+//    the lane's elements of MFMA steps 2j and 2j + 1), the f32 scales of the padded rows behind it.  A lane loads 2 x 16 bytes per tile and K block, keeps the
+//    codes in the two register sets and expands them (exactly) to the bf16 operands right in front of the MFMAs that read them: the MFMA sequence is the bf16
+//    instance's, and the epilogue multiplies the finished f32 sum by the row's scale before the bias (gate and up: each its own), as the stream-K kernel does.
+//  * GATHER: the drafter's input stage fc(cat(embed[ids] * scale, hidden)) for prefills -- `A` is hidden [M, hsplit], K = 2 * hsplit, and a K block below
+//    hsplit comes from the row's embedding row, scaled and re-rounded to bf16 like the stream-K kernel's a_frag (hsplit % 64 == 0: a block never straddles the seam).
 constexpr int TG_BM = 128, TG_THREADS = 256, TG_LDA = 72;          // LDS row stride in bf16 elements (64 + 8 pad)
 
-template <int EPI>
+struct TgGather {
+    const int64_t *ids;
+    const uint16_t *embed;
+    int hsplit, vocab;
+    float embed_scale;
+};
+
+template <int EPI, bool W8 = false, bool GATHER = false>
 __global__ __launch_bounds__(TG_THREADS, 2) void linear_rows_tiled_kernel(const uint16_t *__restrict__ A, const uint16_t *__restrict__ Wp,
                                                                        const uint16_t *__restrict__ bias, int M, int K, int n_rows,
                                                                        uint16_t *__restrict__ out, int out_stride, const uint16_t *__restrict__ aux,
-                                                                       int aux_stride, int pair_rows) {
+                                                                       int aux_stride, int pair_rows, const TgGather ga) {
+    static_assert(!GATHER || EPI == 0, "the input stage has a bias and nothing else behind it");
+    using wreg_t = typename std::conditional<W8, uint4, bf16x8_t>::type;          // W8: 16 codes = the lane's elements of two MFMA steps
+    constexpr int WQ = W8 ? 2 : 4;                                                // registers of a (tile, K block) per lane
     constexpr int NSET = EPI == 2 ? 2 : 1;
     __shared__ alignas(16) uint16_t sA[2][TG_BM * TG_LDA];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1165,17 +1173,26 @@ __global__ __launch_bounds__(TG_THREADS, 2) void linear_rows_tiled_kernel(const 
         int t = EPI == 2 ? (int)blockIdx.y * 2 + wn : (int)blockIdx.y * 4 + wn * 2 + s_;
         tile[s_] = t;
         if (t >= n_tiles) t = n_tiles - 1;          // (a surplus tile contracts the last one again and stores nothing)
-        boff[s_] = ((size_t)t * nb * NSET + (EPI == 2 ? s_ : 0)) * 2048 + lane * 8;
+        boff[s_] = ((size_t)t * nb * NSET + (EPI == 2 ? s_ : 0)) * 2048 + lane * (W8 ? 16 : 8);          // (W8: bytes, else bf16 elements)
     }
+    const uint8_t *Wp8 = reinterpret_cast<const uint8_t *>(Wp);
+    // W8: scale of padded row n of set s at wscale[s * 32 n_tiles + n], behind the brick stream
+    const float *wscale = W8 ? reinterpret_cast<const float *>(Wp8 + (size_t)n_tiles * 32 * K * NSET) : nullptr;
     // A: thread -> four 16-byte chunks of the 128 x 64 block (chunk c of row i / 8 ... coalesced 128-byte rows)
     const uint16_t *ag[4];
+    const uint16_t *eg[GATHER ? 4 : 1];          // GATHER: the same chunk of the row's embedding row
     bool alive[4];
     int lds_off[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int ch = tid + i * TG_THREADS, row = ch >> 3, c = ch & 7;
         alive[i] = m0 + row < M;
-        ag[i] = A + (size_t)(alive[i] ? m0 + row : 0) * K + c * 8;
+        ag[i] = A + (size_t)(alive[i] ? m0 + row : 0) * (GATHER ? ga.hsplit : K) + c * 8;
+        if constexpr (GATHER) {
+            int64_t id = alive[i] ? ga.ids[m0 + row] : 0;
+            id = id < 0 ? 0 : (id >= ga.vocab ? ga.vocab - 1 : id);
+            eg[i] = ga.embed + (size_t)id * ga.hsplit + c * 8;
+        }
         lds_off[i] = row * TG_LDA + c * 8;
     }
     f32x16_t acc[2][2];
@@ -1186,22 +1203,45 @@ __global__ __launch_bounds__(TG_THREADS, 2) void linear_rows_tiled_kernel(const 
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[s_][mt][i] = 0.0f;
     uint4 areg[4];
-    bf16x8_t w0[2][4], w1[2][4];          // (two named sets, not an indexed array: a run-time index would put them in scratch)
+    wreg_t w0[2][WQ], w1[2][WQ];          // (two named sets, not an indexed array: a run-time index would put them in scratch)
     auto load_a = [&](int kb) {
+        if constexpr (GATHER) {
+            const int k0 = kb * 64;          // (uniform: the whole block is embedding or hidden)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) areg[i] = alive[i] ? *reinterpret_cast<const uint4 *>(ag[i] + (size_t)kb * 64) : make_uint4(0, 0, 0, 0);
+            for (int i = 0; i < 4; ++i)
+                areg[i] = !alive[i] ? make_uint4(0, 0, 0, 0) : *reinterpret_cast<const uint4 *>(k0 < ga.hsplit ? eg[i] + k0 : ag[i] + (k0 - ga.hsplit));
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) areg[i] = alive[i] ? *reinterpret_cast<const uint4 *>(ag[i] + (size_t)kb * 64) : make_uint4(0, 0, 0, 0);
+        }
     };
-    auto store_a = [&](int buf) {
+    // (kb: the block areg holds.  GATHER: an embedding block is scaled here, behind the MFMAs its loads flew under -- inputs_embeds * embed_upscale, rounded to
+    // bf16, cnets_lumina_mgpt.py:1096-1097, only for a scale above 1 like the stream-K form)
+    auto store_a = [&](int buf, int kb) {
+        if constexpr (GATHER) {
+            if (kb * 64 < ga.hsplit && ga.embed_scale > 1.0f) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) areg[i] = scale_bf16x8(areg[i], ga.embed_scale);
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4 *>(&sA[buf][lds_off[i]]) = areg[i];
     };
-    auto load_w = [&](int kb, bf16x8_t (&w)[2][4]) {
+    auto load_w = [&](int kb, wreg_t (&w)[2][WQ]) {
 #pragma unroll
         for (int s_ = 0; s_ < 2; ++s_)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) w[s_][q] = load_frag(Wp + boff[s_] + (size_t)kb * NSET * 2048 + q * 512);
+            for (int q = 0; q < WQ; ++q) {
+                if constexpr (W8) w[s_][q] = load_w8(Wp8 + boff[s_] + (size_t)kb * NSET * 2048 + q * 1024);
+                else w[s_][q] = load_frag(Wp + boff[s_] + (size_t)kb * NSET * 2048 + q * 512);
+            }
     };
-    auto compute = [&](int buf, const bf16x8_t (&w)[2][4]) {
+    // the B operand of MFMA step q
+    auto w_frag = [&](const wreg_t &v, int q) -> bf16x8_t {
+        if constexpr (W8) return fp8x8_to_bf16x8((q & 1) ? make_uint2(v.z, v.w) : make_uint2(v.x, v.y));
+        else return v;
+    };
+    auto compute = [&](int buf, const wreg_t (&w)[2][WQ]) {
         // the four accumulators take turns (an MFMA that adds to the accumulator of the one before it waits out its whole latency)
         bf16x8_t af[2][4];
 #pragma unroll
@@ -1211,15 +1251,17 @@ __global__ __launch_bounds__(TG_THREADS, 2) void linear_rows_tiled_kernel(const 
             for (int q = 0; q < 4; ++q) af[mt][q] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4 *>(arow + 8 * q));
         }
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
+        for (int q = 0; q < 4; ++q) {
+            const bf16x8_t wq[2] = {w_frag(w[0][W8 ? q >> 1 : q], q), w_frag(w[1][W8 ? q >> 1 : q], q)};
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                for (int s_ = 0; s_ < 2; ++s_) acc[s_][mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mt][q], w[s_][q], acc[s_][mt], 0, 0, 0);
+                for (int s_ = 0; s_ < 2; ++s_) acc[s_][mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mt][q], wq[s_], acc[s_][mt], 0, 0, 0);
+        }
     };
     load_a(0);
     load_w(0, w0);
-    store_a(0);
+    store_a(0, 0);
     __syncthreads();
     for (int kb = 0; kb < nb; kb += 2) {
         if (kb + 1 < nb) {
@@ -1227,7 +1269,7 @@ __global__ __launch_bounds__(TG_THREADS, 2) void linear_rows_tiled_kernel(const 
             load_w(kb + 1, w1);
         }
         compute(0, w0);
-        if (kb + 1 < nb) store_a(1);          // (the other buffer: its readers finished before the previous barrier)
+        if (kb + 1 < nb) store_a(1, kb + 1);          // (the other buffer: its readers finished before the previous barrier)
         __syncthreads();
         if (kb + 1 >= nb) break;
         if (kb + 2 < nb) {
@@ -1235,7 +1277,7 @@ __global__ __launch_bounds__(TG_THREADS, 2) void linear_rows_tiled_kernel(const 
             load_w(kb + 2, w0);
         }
         compute(1, w1);
-        if (kb + 2 < nb) store_a(0);
+        if (kb + 2 < nb) store_a(0, kb + 2);
         __syncthreads();
     }
     // epilogue from the accumulators: element (row = (reg & 3) + 8 (reg >> 2) + 4 h, column r) of each 32 x 32 tile
@@ -1249,6 +1291,7 @@ __global__ __launch_bounds__(TG_THREADS, 2) void linear_rows_tiled_kernel(const 
                 const int n = tile[0] * 32 + r;
                 if (tile[0] < n_tiles && n < n_rows) {
                     float g = acc[0][mt][reg], u = acc[1][mt][reg];
+                    if constexpr (W8) { g *= wscale[n]; u *= wscale[n_tiles * 32 + n]; }
                     if (bias) { g += bf16_bits_to_f32(bias[n]); u += bf16_bits_to_f32(bias[pair_rows + n]); }
                     const float gb = bf16_bits_to_f32(f32_to_bf16_rne(g)), ub = bf16_bits_to_f32(f32_to_bf16_rne(u));
                     const float sg = bf16_bits_to_f32(f32_to_bf16_rne(gb / (1.0f + expf(-gb))));
@@ -1260,6 +1303,7 @@ __global__ __launch_bounds__(TG_THREADS, 2) void linear_rows_tiled_kernel(const 
                     const int n = tile[s_] * 32 + r;
                     if (tile[s_] < n_tiles && n < n_rows) {
                         float v = acc[s_][mt][reg];
+                        if constexpr (W8) v *= wscale[n];
                         if (bias) v += bf16_bits_to_f32(bias[n]);
                         uint16_t o = f32_to_bf16_rne(v);
                         if constexpr (EPI == 1) o = f32_to_bf16_rne(bf16_bits_to_f32(aux[(size_t)m * aux_stride + n]) + bf16_bits_to_f32(o));
@@ -1270,28 +1314,49 @@ __global__ __launch_bounds__(TG_THREADS, 2) void linear_rows_tiled_kernel(const 
         }
 }
 
+// the argument checks of lantern_linear_rows_packed and lantern_linear_rows_packed_fmt (nothing here touches the GPU)
+static int linear_rows_packed_check(const char *who, const void *A, const void *W_packed, int M, int K, int n_rows, const void *out, int out_stride, int epilogue,
+                                    const void *aux, int aux_stride, int pair_rows) {
+    LANTERN_CHECK_ARG(A && W_packed && out, "%s: null buffer", who);
+    LANTERN_CHECK_ARG(M >= 0 && K > 0 && K % 64 == 0 && n_rows >= 0 && out_stride >= n_rows, "%s: K=%d must be a multiple of 64, out rows hold n_rows", who, K);
+    LANTERN_CHECK_ARG(epilogue == 0 || epilogue == LANTERN_EPI_RESIDUAL || epilogue == LANTERN_EPI_SILU_MUL, "%s: epilogue %d", who, epilogue);
+    if (epilogue == LANTERN_EPI_RESIDUAL) LANTERN_CHECK_ARG(aux && aux_stride >= n_rows, "%s: the residual [M, aux_stride >= n_rows] is missing", who);
+    if (epilogue == LANTERN_EPI_SILU_MUL) LANTERN_CHECK_ARG(pair_rows > 0, "%s: pair_rows = rows of the gate half of the packed gate / up pair", who);
+    if (M > 0 && n_rows > 0) LANTERN_CHECK_ARG((M + 63) / 64 <= 65535, "%s: M=%d rows exceed the launch grid", who, M);
+    return LANTERN_OK;
+}
+
+// the LDS-tiled form (128 x 128 per workgroup; row blocks fastest so that a weight tile's readers are neighbours) on a weight of either format
+static int launch_linear_rows_tiled(const char *who, const void *A, const void *W_packed, const void *bias, int M, int K, int n_rows, void *out, int out_stride,
+                                    int epilogue, const void *aux, int aux_stride, int pair_rows, bool fp8, hipStream_t st) {
+    const uint16_t *a = (const uint16_t *)A, *w = (const uint16_t *)W_packed, *bi = (const uint16_t *)bias, *ax = (const uint16_t *)aux;
+    uint16_t *o = (uint16_t *)out;
+    const int tiles = (n_rows + 31) / 32;
+    const dim3 grid((M + TG_BM - 1) / TG_BM, epilogue == LANTERN_EPI_SILU_MUL ? (tiles + 1) / 2 : (tiles + 3) / 4);
+    const TgGather none{};
+#define TG_LAUNCH(E_, PAIR_)                                                                                                                                        \
+    do {                                                                                                                                                            \
+        if (fp8) LANTERN_LAUNCH((linear_rows_tiled_kernel<E_, true>), grid, dim3(TG_THREADS), 0, st, a, w, bi, M, K, n_rows, o, out_stride, ax, aux_stride, PAIR_, none); \
+        else LANTERN_LAUNCH((linear_rows_tiled_kernel<E_>), grid, dim3(TG_THREADS), 0, st, a, w, bi, M, K, n_rows, o, out_stride, ax, aux_stride, PAIR_, none);       \
+    } while (0)
+    if (epilogue == LANTERN_EPI_SILU_MUL) TG_LAUNCH(2, pair_rows);
+    else if (epilogue == LANTERN_EPI_RESIDUAL) TG_LAUNCH(1, 0);
+    else TG_LAUNCH(0, 0);
+#undef TG_LAUNCH
+    LANTERN_CHECK_LAUNCH(who);
+    return LANTERN_OK;
+}
+
 extern "C" int lantern_linear_rows_packed(const void *A, const void *W_packed, const void *bias, int M, int K, int n_rows, void *out, int out_stride,
                                           int epilogue, const void *aux, int aux_stride, int pair_rows, void *stream) {
-    LANTERN_CHECK_ARG(A && W_packed && out, "linear_rows_packed: null buffer");
-    LANTERN_CHECK_ARG(M >= 0 && K > 0 && K % 64 == 0 && n_rows >= 0 && out_stride >= n_rows, "linear_rows_packed: K=%d must be a multiple of 64, out rows hold n_rows", K);
-    LANTERN_CHECK_ARG(epilogue == 0 || epilogue == LANTERN_EPI_RESIDUAL || epilogue == LANTERN_EPI_SILU_MUL, "linear_rows_packed: epilogue %d", epilogue);
-    if (epilogue == LANTERN_EPI_RESIDUAL) LANTERN_CHECK_ARG(aux && aux_stride >= n_rows, "linear_rows_packed: the residual [M, aux_stride >= n_rows] is missing");
-    if (epilogue == LANTERN_EPI_SILU_MUL) LANTERN_CHECK_ARG(pair_rows > 0, "linear_rows_packed: pair_rows = rows of the gate half of the packed gate / up pair");
+    if (const int rc = linear_rows_packed_check("linear_rows_packed", A, W_packed, M, K, n_rows, out, out_stride, epilogue, aux, aux_stride, pair_rows)) return rc;
     if (M == 0 || n_rows == 0) return LANTERN_OK;
     hipStream_t st = (hipStream_t)stream;
     const uint16_t *a = (const uint16_t *)A, *w = (const uint16_t *)W_packed, *bi = (const uint16_t *)bias, *ax = (const uint16_t *)aux;
     uint16_t *o = (uint16_t *)out;
     const int tiles = (n_rows + 31) / 32;
-    LANTERN_CHECK_ARG((M + 63) / 64 <= 65535, "linear_rows_packed: M=%d rows exceed the launch grid", M);
-    const int tiled_from = tuning(TUNE_GEMM_TILED_FROM);
-    if (M >= tiled_from) {          // many rows: the LDS-tiled form (128 x 128 per workgroup; row blocks fastest so that a weight tile's readers are neighbours)
-        const dim3 grid((M + TG_BM - 1) / TG_BM, epilogue == LANTERN_EPI_SILU_MUL ? (tiles + 1) / 2 : (tiles + 3) / 4);
-        if (epilogue == LANTERN_EPI_SILU_MUL) LANTERN_LAUNCH((linear_rows_tiled_kernel<2>), grid, dim3(TG_THREADS), 0, st, a, w, bi, M, K, n_rows, o, out_stride, ax, aux_stride, pair_rows);
-        else if (epilogue == LANTERN_EPI_RESIDUAL) LANTERN_LAUNCH((linear_rows_tiled_kernel<1>), grid, dim3(TG_THREADS), 0, st, a, w, bi, M, K, n_rows, o, out_stride, ax, aux_stride, 0);
-        else LANTERN_LAUNCH((linear_rows_tiled_kernel<0>), grid, dim3(TG_THREADS), 0, st, a, w, bi, M, K, n_rows, o, out_stride, ax, aux_stride, 0);
-        LANTERN_CHECK_LAUNCH("linear_rows_packed");
-        return LANTERN_OK;
-    }
+    if (M >= tuning(TUNE_GEMM_TILED_FROM))          // many rows
+        return launch_linear_rows_tiled("linear_rows_packed", A, W_packed, bias, M, K, n_rows, out, out_stride, epilogue, aux, aux_stride, pair_rows, false, st);
 #define LRP_LAUNCH(MT_, E_)                                                                                                                         \
     LANTERN_LAUNCH((linear_rows_packed_kernel<MT_, E_>), dim3(tiles, (M + MT_ * 32 - 1) / (MT_ * 32)), dim3(FC_THREADS), 0, st, a, w, bi, M, K, n_rows, o, \
                    out_stride, ax, aux_stride, epilogue == LANTERN_EPI_SILU_MUL ? pair_rows : 0)
@@ -1309,6 +1374,39 @@ extern "C" int lantern_linear_rows_packed(const void *A, const void *W_packed, c
     }
 #undef LRP_LAUNCH
     LANTERN_CHECK_LAUNCH("linear_rows_packed");
+    return LANTERN_OK;
+}
+
+// The same entry with the weight's format as an argument.  An FP8 weight takes the tiled kernel at EVERY row count: there is no fp8 row-blocked kernel, and the
+// gemm_tiled_from tuning value (a choice between two bf16 kernels) does not apply to it.
+extern "C" int lantern_linear_rows_packed_fmt(const void *A, const void *W_packed, const void *bias, int M, int K, int n_rows, void *out, int out_stride,
+                                              int epilogue, const void *aux, int aux_stride, int pair_rows, int packed, void *stream) {
+    LANTERN_CHECK_ARG(packed == LANTERN_PACKED_BF16 || packed == LANTERN_PACKED_FP8,
+                      "linear_rows_packed_fmt: packed = %d: the weight must be packed, LANTERN_PACKED_BF16 (1) or LANTERN_PACKED_FP8 (2)", packed);
+    if (packed == LANTERN_PACKED_BF16) return lantern_linear_rows_packed(A, W_packed, bias, M, K, n_rows, out, out_stride, epilogue, aux, aux_stride, pair_rows, stream);
+    if (const int rc = linear_rows_packed_check("linear_rows_packed_fmt", A, W_packed, M, K, n_rows, out, out_stride, epilogue, aux, aux_stride, pair_rows)) return rc;
+    if (M == 0 || n_rows == 0) return LANTERN_OK;
+    return launch_linear_rows_tiled("linear_rows_packed_fmt", A, W_packed, bias, M, K, n_rows, out, out_stride, epilogue, aux, aux_stride, pair_rows, true,
+                                    (hipStream_t)stream);
+}
+
+// O11 for prefills (any M) on the packed [H, 2H] weight of either format: the GATHER instances of the tiled kernel
+extern "C" int lantern_drafter_fc_packed(const int64_t *ids, const void *hidden, const void *embed, const void *W_packed, const void *bias, int M, int H, int vocab,
+                                         float embed_scale, void *out, int packed, void *stream) {
+    LANTERN_CHECK_ARG(ids && hidden && embed && W_packed && out, "drafter_fc_packed: null buffer");
+    LANTERN_CHECK_ARG(packed == LANTERN_PACKED_BF16 || packed == LANTERN_PACKED_FP8,
+                      "drafter_fc_packed: packed = %d: the weight must be packed, LANTERN_PACKED_BF16 (1) or LANTERN_PACKED_FP8 (2)", packed);
+    LANTERN_CHECK_ARG(M >= 0 && H > 0 && H % 64 == 0 && vocab > 0, "drafter_fc_packed: M=%d >= 0, H=%d a multiple of 64", M, H);
+    LANTERN_CHECK_ARG((M + 63) / 64 <= 65535, "drafter_fc_packed: M=%d rows exceed the launch grid", M);
+    if (M == 0) return LANTERN_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((M + TG_BM - 1) / TG_BM, (H / 32 + 3) / 4);
+    TgGather ga{};
+    ga.ids = ids; ga.embed = (const uint16_t *)embed; ga.hsplit = H; ga.vocab = vocab; ga.embed_scale = embed_scale;
+    const uint16_t *h = (const uint16_t *)hidden, *w = (const uint16_t *)W_packed, *bi = (const uint16_t *)bias, *none = nullptr;
+    if (packed == LANTERN_PACKED_FP8) LANTERN_LAUNCH((linear_rows_tiled_kernel<0, true, true>), grid, dim3(TG_THREADS), 0, st, h, w, bi, M, 2 * H, H, (uint16_t *)out, H, none, 0, 0, ga);
+    else LANTERN_LAUNCH((linear_rows_tiled_kernel<0, false, true>), grid, dim3(TG_THREADS), 0, st, h, w, bi, M, 2 * H, H, (uint16_t *)out, H, none, 0, 0, ga);
+    LANTERN_CHECK_LAUNCH("drafter_fc_packed");
     return LANTERN_OK;
 }
 

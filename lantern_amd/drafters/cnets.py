@@ -590,12 +590,14 @@ class Model(nn.Module):
             emb = self.embed_tokens.weight
             emb = emb if emb.dtype == torch.bfloat16 else emb.to(torch.bfloat16)
             ids, hid = input_ids.reshape(-1), hidden_states.reshape(B * T, H)
-            out = torch.empty_like(hid)
-            fp8 = self.weight_format == "fp8"          # (fp8: every row count on the packed weight, prefills in 32-row blocks -- ops.drafter_fc)
+            fp8 = self.weight_format == "fp8"          # (fp8: every row count on the packed weight -- ops.drafter_fc)
             pk = self._packed_weight("fc", w) if ((B * T <= 32 or fp8) and H % 64 == 0) else None          # the drafting shape streams the packed weight
-            for s in range(0, B * T, 128):                     # one drafter call is <= ~120 rows; prefills go in slices
-                out[s:s + 128] = ops.drafter_fc(ids[s:s + 128], hid[s:s + 128], emb, w, self.fc.bias,
-                                                embed_scale=float(self.embed_upscale) if self.embed_upscale > 1.0 else 1.0, packed=pk)
+            scale = float(self.embed_upscale) if self.embed_upscale > 1.0 else 1.0
+            if fp8 and B * T > 128:                            # an fp8 prefill: every row in one launch of the tiled kernel's gather form
+                return ops.drafter_fc(ids, hid, emb, w, self.fc.bias, embed_scale=scale, packed=pk).view(B, T, H)
+            out = torch.empty_like(hid)
+            for s in range(0, B * T, 128):                     # one drafter call is <= ~120 rows; bf16 prefills go in slices
+                out[s:s + 128] = ops.drafter_fc(ids[s:s + 128], hid[s:s + 128], emb, w, self.fc.bias, embed_scale=scale, packed=pk)
             return out.view(B, T, H)
         # other dtypes (f32 checkpoints in tests): the same arithmetic in torch on the device
         e = self.embed_tokens(input_ids).to(hidden_states.dtype)

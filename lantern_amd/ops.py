@@ -760,7 +760,8 @@ def linear_rows_streamk(A, weight, epilogue: int = 0, n_rows: Optional[int] = No
 
 def linear_rows_packed(A, weight: "PackedLinearWeight", epilogue: int = 0, bias=None, residual=None):
     """A [M, K] bf16 (ANY number of rows: the drafter's prompt prefill) @ the packed weight, epilogues as linear_rows_streamk
-    (lantern_linear_rows_packed: row blocks of 128 -- 64 for a gate / up pair -- re-stream the weight tile)."""
+    (lantern_linear_rows_packed: row blocks of 128 -- 64 for a gate / up pair -- re-stream the weight tile).  An fp8 weight: from "gemm_tiled_from" rows
+    (default 129) one launch of the tiled fp8 kernel (lantern_linear_rows_packed_fmt), below that the stream-K kernel in blocks of 32 rows."""
     if not isinstance(weight, PackedLinearWeight):
         raise _lib.LanternError("linear_rows_packed: weight must be a PackedLinearWeight (pack_linear_weight)")
     if not A.is_cuda or A.dtype != torch.bfloat16:
@@ -769,8 +770,8 @@ def linear_rows_packed(A, weight: "PackedLinearWeight", epilogue: int = 0, bias=
     M, K = A.shape
     if K != weight.K or (epilogue == EPI_SILU_MUL) != (weight.pair_rows > 0):
         raise _lib.LanternError("linear_rows_packed: the packed weight does not match this call (K, gate / up pairing)")
-    if weight.fmt == "fp8":
-        # no tiled fp8 kernel: the rows go through the stream-K kernel in blocks of at most 32 (the prefill runs once per image; cost in EXPERIMENTS.md)
+    if weight.fmt == "fp8" and M < _lib.get_tuning("gemm_tiled_from"):
+        # 33 - 128 rows have no fp8 kernel of their own: they go through the stream-K kernel in blocks of at most 32
         if M == 0:
             return torch.empty((0, weight.n_rows), dtype=torch.bfloat16, device=A.device)
         return torch.cat([linear_rows_streamk(A[m0:m0 + 32], weight, epilogue, bias=bias, residual=None if residual is None else residual[m0:m0 + 32])
@@ -778,6 +779,11 @@ def linear_rows_packed(A, weight: "PackedLinearWeight", epilogue: int = 0, bias=
     out = torch.empty((M, weight.n_rows), dtype=torch.bfloat16, device=A.device)
     r = None if residual is None else residual.contiguous()
     b = None if bias is None else bias.contiguous()
+    if weight.fmt == "fp8":
+        check(_lib.lib().lantern_linear_rows_packed_fmt(C.c_void_p(A.data_ptr()), C.c_void_p(weight.data.data_ptr()), C.c_void_p(_ptr(b)), M, K, weight.n_rows,
+                                                        C.c_void_p(out.data_ptr()), weight.n_rows, int(epilogue), C.c_void_p(_ptr(r)), 0 if r is None else r.shape[1],
+                                                        int(weight.pair_rows), weight.code, _stream()), "linear_rows_packed_fmt")
+        return out
     check(_lib.lib().lantern_linear_rows_packed(C.c_void_p(A.data_ptr()), C.c_void_p(weight.data.data_ptr()), C.c_void_p(_ptr(b)), M, K, weight.n_rows,
                                                 C.c_void_p(out.data_ptr()), weight.n_rows, int(epilogue), C.c_void_p(_ptr(r)), 0 if r is None else r.shape[1],
                                                 int(weight.pair_rows), _stream()), "linear_rows_packed")
@@ -949,7 +955,8 @@ def mask_left_padding(attention_mask, out=None):
 def drafter_fc(ids, hidden, embed, weight, bias=None, embed_scale: float = 1.0, packed: Optional["PackedLinearWeight"] = None):
     """O11 (MFMA): fc(cat(embed[ids] * scale, hidden)) -> bf16 [M,H].  ids [M] i64, hidden [M,H] bf16, embed [vocab,H] bf16,
     weight [H,2H] bf16 (nn.Linear layout), bias [H] bf16 or None.  Up to 32 rows with H % 64 == 0 (the drafting shape) take the stream-K
-    kernel, on `packed` = pack_linear_weight(weight) when given."""
+    kernel, on `packed` = pack_linear_weight(weight) when given.  An fp8 `packed` at prefill row counts ("gemm_tiled_from" rows and more, default 129): one
+    launch of the tiled kernel's gather form (lantern_drafter_fc_packed); 33 rows up to that threshold: stream-K blocks of 32."""
     for t, n in ((hidden, "hidden"), (embed, "embed"), (weight, "weight")):
         if not t.is_cuda or t.dtype != torch.bfloat16:
             raise _lib.LanternError(f"drafter_fc: {n} must be a bf16 device tensor")
@@ -960,9 +967,16 @@ def drafter_fc(ids, hidden, embed, weight, bias=None, embed_scale: float = 1.0, 
     out = torch.empty((M, H), dtype=torch.bfloat16, device=hidden.device)
     b = None if bias is None else bias.contiguous()
     if packed is not None and packed.fmt == "fp8" and (M > 32 or H % 64):
-        # fp8 weights exist for the stream-K kernel only: more rows go through it in blocks of 32 (never onto the bf16 row-major weight unnoticed)
         if H % 64:
             raise _lib.LanternError(f"drafter_fc: an fp8 packed weight needs H % 64 == 0 (H = {H})")
+        if M >= _lib.get_tuning("gemm_tiled_from"):
+            if packed.K != 2 * H or packed.n_rows != H or packed.pair_rows:
+                raise _lib.LanternError("drafter_fc: the packed weight is not this fc's [H, 2H] weight")
+            check(_lib.lib().lantern_drafter_fc_packed(C.c_void_p(ids.data_ptr()), C.c_void_p(hidden.data_ptr()), C.c_void_p(embed.data_ptr()),
+                                                       C.c_void_p(packed.data.data_ptr()), C.c_void_p(_ptr(b)), M, H, embed.shape[0], C.c_float(embed_scale),
+                                                       C.c_void_p(out.data_ptr()), packed.code, _stream()), "drafter_fc_packed")
+            return out
+        # 33 rows up to the tiled kernel's threshold go through the stream-K kernel in blocks of 32 (never onto the bf16 row-major weight unnoticed)
         return torch.cat([drafter_fc(ids[m0:m0 + 32], hidden.reshape(M, H)[m0:m0 + 32], embed, weight, bias, embed_scale, packed) for m0 in range(0, M, 32)], dim=0)
     if M <= 32 and H % 64 == 0:
         if packed is not None and (packed.K != 2 * H or packed.n_rows != H or packed.pair_rows):

@@ -1,8 +1,10 @@
 """The drafter's prompt prefill (first call of topK_generate: the whole prompt through cnets.Model.forward) at the 7B layer size: the HIP path
 (drafter_fc slices, lantern_linear_rows_packed, head stage, block-causal lantern_tree_attention) against the same model on torch's ops
 (F.linear = hipBLASLt, eager softmax attention under the additive mask), milliseconds per call between HIP events.
-usage: prefill_bench.py [--weight-format bf16|fp8] [prompt tokens=600] [reps=5]
-(--weight-format fp8: there is no tiled fp8 kernel -- the prefill's GEMMs go through the stream-K kernel in blocks of 32 rows)"""
+usage: prefill_bench.py [--weight-format bf16|fp8] [--input-stage] [prompt tokens=600] [reps=5]
+(--weight-format fp8: from 129 rows the layer's GEMMs and the input stage run the tiled kernel's fp8 instances, one launch each -- lantern_linear_rows_packed_fmt,
+lantern_drafter_fc_packed; 33 - 128 rows go through the stream-K kernel in blocks of 32 rows.
+--input-stage: also time the input stage alone, fc(cat(embed[ids] * scale, hidden)) on the same rows, as "ms_input_stage" in the JSON line)"""
 import json, os, sys, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -23,6 +25,9 @@ def _take_option(name, default, choices=None):
 
 
 WEIGHT_FORMAT = _take_option("--weight-format", "bf16", ("bf16", "fp8"))
+INPUT_STAGE = "--input-stage" in sys.argv
+if INPUT_STAGE:
+    sys.argv.remove("--input-stage")
 
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 600
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -58,7 +63,22 @@ def timed():
     return e0.elapsed_time(e1) / reps, y
 
 
+def timed_input_stage():
+    """cnets.Model._input_stage alone on the prefill's rows (what forward runs in front of the layer)"""
+    with torch.no_grad():
+        mdl._input_stage(x, ids)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            mdl._input_stage(x, ids)
+        e1.record()
+        torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
 ms_hip, y_hip = timed()
+extra = {"ms_input_stage": round(timed_input_stage(), 3)} if INPUT_STAGE else {}
 for l in mdl.layers:
     l.fused = False
     l.inplace_cache = False
@@ -67,4 +87,4 @@ ms_torch, y_torch = timed()
 w_bytes = sum(p.numel() * 2 for p in mdl.layers[0].parameters())
 flops = 2 * 2 * T * (w_bytes // 2)
 print(json.dumps({"rows": 2 * T, "weight_format": WEIGHT_FORMAT, "ms_hip": round(ms_hip, 3), "ms_torch_ops": round(ms_torch, 3), "layer_weight_MB": round(w_bytes / 1e6, 1),
-                  "layer_gemm_TFLOPs_hip": round(flops / ms_hip / 1e9, 1), "max_abs_diff_valid_rows": float((y_hip[:, 9:].float() - y_torch[:, 9:].float()).abs().max())}))
+                  "layer_gemm_TFLOPs_hip": round(flops / ms_hip / 1e9, 1), "max_abs_diff_valid_rows": float((y_hip[:, 9:].float() - y_torch[:, 9:].float()).abs().max()), **extra}))
