@@ -481,9 +481,14 @@ typedef struct lantern_step_group {
      * COMPLETED by all groups; behind it, one 128-byte line per counter, each group's "workgroups of my running commit launch that have finished"
      * counters in two levels (32 first-level lines per group, then one: thousands of workgroups adding to one word serialise at the memory side); the
      * workgroup that fills a counter puts it back to zero, the launch's last workgroup increments word 0.  This step's evaluate_posterior (chain kernel)
-     * holds its last instructions until turn[0] >= turn_wait -- bounded: after ~40 ms it proceeds anyway, turn-taking is scheduling, never correctness
-     * -- and the commit launched behind it releases the turn when it is done.  turn_wait: the commits that must have completed before this one starts
-     * (ticket - (window - 1) for `window` commits in flight; the harness issues tickets step * n_groups + group).
+     * holds its last instructions until turn[0] >= turn_wait -- bounded: after 2 ms of the constant-rate wall clock it proceeds anyway, turn-taking is
+     * scheduling, never correctness -- and the commit launched behind it releases the turn when it is done.  A workgroup that gave up adds 1 to word 1
+     * (the spare second word of the first line): zero after a healthy run; a caller that finds it non-zero has correct results and a schedule in which
+     * some wait could not be met in time (a ticket nothing releases, or a step far longer than 2 ms).  turn_wait: the commits that must have
+     * completed before this one starts (ticket - (window - 1) for `window` commits in flight; the harness issues tickets step * n_groups + group).
+     * Within one call the groups that share `turn` have distinct turn_group (refused otherwise); they may share a stream.  lantern_verify_step enqueues
+     * the launches that wait in ticket order (ascending turn_wait, each walk with its commit right behind it), so that every wait targets a launch
+     * enqueued earlier, whatever hardware queues the streams were given; tickets grow from call to call.
      * Independent sequences: any order is correct; the reference runs one sequence per process and has no counterpart. */
     int64_t *turn;
     int32_t turn_group, turn_groups;        /* this group's index, and how many groups share `turn` */
@@ -510,6 +515,10 @@ typedef struct lantern_step_group {
 #define LANTERN_STEP_PREPARED 2           /* the previous call's commit launch already ran this group's lantern_prepare_step (prepare_next); only valid on a
                                              static-tree group with a node_list, refused otherwise */
 int lantern_verify_step(const lantern_step_group *groups, int n_groups);
+/* Diagnostic for callers that place stream groups (the benchmark harness): *shared = 1 when stream_b's work cannot start while a kernel runs on stream_a
+ * -- both were given the same hardware queue, or are the same stream --, else 0.  Two tiny kernels (one polls a flag for at most ~200 us, the other
+ * sets it), three attempts before it says 1; synchronises both streams, so not for the hot path.  Groups on one hardware queue run one after the other. */
+int lantern_streams_share_queue(void *stream_a, void *stream_b, int *shared);
 /* O6 + O7 restricted to s->node_list in one launch (bf16 Lumina rows, 8192-id window): candidates -> s->tree_cand / cand / cart_prob,
  * probabilities of the listed rows -> s->out_win, their classes -> s->row_hot.  Called by lantern_verify_step when node_list is set.
  * s->dyn != NULL: the tree workgroups run O4 + O6-dynamic (lantern_tree_dynamic_candidates) beside the row workgroups; the listed

@@ -22,6 +22,10 @@
 
 namespace lantern {
 
+// how long a walk waits for its commit turn before it gives up: 2 ms in ticks of wall_clock64(), which runs at a constant 100 MHz on gfx950
+// (hipDeviceAttributeWallClockRate), whatever the core clock does
+constexpr long long EPW_TURN_WAIT_TICKS = 200000;
+
 // ------------------------------------------------------------------------------- O8 windowed
 //
 // Structure (v3).  A 512-thread workgroup owns one sequence.  The serial part of the algorithm -- walking the
@@ -1169,14 +1173,24 @@ __device__ __forceinline__ int epw_body(const EpwArgs &args, const int b, const 
         }
     }
     // commit turn-taking (lantern_step_group.turn): everything is written; the workgroup's last act is to wait for its group's turn, so that the commit
-    // launched behind this kernel on the stream starts then.  Bounded (~40 ms): the turn is scheduling, never correctness.
+    // launched behind this kernel on the stream starts then.  Bounded by TIME: EPW_TURN_WAIT_TICKS of the constant-rate wall clock (2 ms, more than 15
+    // times the longest step on record), because the turn is scheduling, never correctness.  A workgroup that gives up says so in turn[1] (the spare
+    // second word of the first line; lantern_step_group.turn): a healthy run leaves it at zero.  (The iteration count only backstops a clock that
+    // does not advance; at ~0.5 us per iteration it is far beyond the time bound.)
     if (ka->win.turn) {
         if (tid == 0) {
             const long long need = ka->win.turn_wait;
+            const long long t0 = wall_clock64();
+            bool released = false;
             for (int spins = 0; spins < 200000; ++spins) {
-                if ((long long)__hip_atomic_load(ka->win.turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= need) break;
+                if ((long long)__hip_atomic_load(ka->win.turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= need) {
+                    released = true;
+                    break;
+                }
+                if (wall_clock64() - t0 > EPW_TURN_WAIT_TICKS) break;
                 __builtin_amdgcn_s_sleep(16);
             }
+            if (!released) __hip_atomic_fetch_add(const_cast<int64_t *>(ka->win.turn) + 1, (int64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     return (best << 8) | a;          // the verdict (uniform): best path, rows kept = accept_len + 1

@@ -43,3 +43,64 @@ extern "C" int lantern_harness_advance(int B, int n_lens, int ld, int64_t tokens
     LANTERN_CHECK_LAUNCH("harness_advance");
     return LANTERN_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Do two streams share a hardware queue?  (The runtime maps every stream to one of a few hardware queues when the stream is first used, and
+// offers no way to ask which.)  A hardware queue runs its packets in order, so: a one-wave kernel on stream A polls a flag for at most
+// PROBE_TICKS of the constant-rate wall clock (100 MHz: ~200 us) and records whether it saw it; a one-thread kernel enqueued right behind it on
+// stream B sets the flag.  On distinct queues the second kernel runs beside the first, which sees the flag within microseconds; on one queue
+// it waits behind the first, which times out.
+namespace lantern {
+constexpr long long PROBE_TICKS = 20000;
+
+__global__ void queue_probe_wait_kernel(int *__restrict__ flag, int *__restrict__ saw) {
+    if (threadIdx.x != 0) return;
+    const long long t0 = wall_clock64();
+    int seen = 0;
+    for (int spins = 0; spins < 100000 && !seen; ++spins) {          // (the count only backstops a clock that does not advance)
+        seen = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+        if (wall_clock64() - t0 > PROBE_TICKS) break;
+        __builtin_amdgcn_s_sleep(8);
+    }
+    saw[0] = seen;
+}
+
+__global__ void queue_probe_set_kernel(int *__restrict__ flag) { __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+}  // namespace lantern
+
+// *shared = 1 if work on stream_b cannot start while a kernel on stream_a runs (one hardware queue; a stream against itself), else 0.  Synchronises both
+// streams.  "Shared" only after three attempts in a row timed out: a host hiccup between the two launches of one attempt must not read as a shared queue.
+extern "C" int lantern_streams_share_queue(void *stream_a, void *stream_b, int *shared) {
+    if (!shared) {
+        lantern::set_error("streams_share_queue: shared is NULL");
+        return LANTERN_E_INVALID;
+    }
+    hipStream_t a = (hipStream_t)stream_a, b = (hipStream_t)stream_b;
+    int *dev = nullptr;          // [0] the flag, [1] what the waiting kernel saw
+    if (hipMalloc(&dev, 2 * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        lantern::set_error("streams_share_queue: hipMalloc failed");
+        return LANTERN_E_LAUNCH;
+    }
+    int rc = LANTERN_OK, saw = 0;
+    for (int attempt = 0; attempt < 3 && rc == LANTERN_OK && !saw; ++attempt) {
+        // both streams idle and the flag cleared before either kernel is enqueued
+        if (hipMemsetAsync(dev, 0, 2 * sizeof(int), a) != hipSuccess || hipStreamSynchronize(a) != hipSuccess || hipStreamSynchronize(b) != hipSuccess) {
+            rc = LANTERN_E_LAUNCH;
+            break;
+        }
+        hipLaunchKernelGGL(lantern::queue_probe_wait_kernel, dim3(1), dim3(64), 0, a, dev, dev + 1);
+        hipLaunchKernelGGL(lantern::queue_probe_set_kernel, dim3(1), dim3(1), 0, b, dev);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(a) != hipSuccess || hipStreamSynchronize(b) != hipSuccess ||
+            hipMemcpy(&saw, dev + 1, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = LANTERN_E_LAUNCH;
+    }
+    (void)hipFree(dev);
+    if (rc != LANTERN_OK) {
+        (void)hipGetLastError();
+        lantern::set_error("streams_share_queue: a launch, copy or synchronise failed");
+        return rc;
+    }
+    *shared = saw ? 0 : 1;
+    return LANTERN_OK;
+}

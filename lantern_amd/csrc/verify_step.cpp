@@ -5,7 +5,9 @@
 // behind the EAGLE-2 drafter (cnets_lumina_mgpt.py:1337-1420 / cnets_llamagen.py:826-912: per-sequence trees).
 #include "prep_dev.h"
 #include "gather_dev.h"
+#include <algorithm>
 #include <cstdio>
+#include <vector>
 
 namespace lantern {
 void set_error(const char *fmt, ...);
@@ -37,7 +39,8 @@ extern "C" int lantern_verify_step(const lantern_step_group *groups, int n_group
         return LANTERN_E_INVALID;
     }
     // stage by stage across the groups: every stream receives its next kernel before any stream receives the one after
-    // (the streams then advance side by side instead of one group running a whole step ahead of the others)
+    // (the streams then advance side by side instead of one group running a whole step ahead of the others) -- up to the walk: the walks and commits of
+    // groups that take commit turns are enqueued in ticket order ("Issue order" below)
     int rc;
     for (int g = 0; g < n_groups; ++g) {          // (before anything is launched: a walk that waits for a turn nobody will release spins out its bound)
         const lantern_step_group &s = groups[g];
@@ -60,6 +63,12 @@ extern "C" int lantern_verify_step(const lantern_step_group *groups, int n_group
             lantern::set_error("commit turn-taking: turn_group in [0, turn_groups) and the group's KV slabs (its commit launch releases the turn)");
             return fail(g, "turn", LANTERN_E_INVALID);
         }
+        for (int h = 0; s.turn && h < g; ++h)          // (two launches counting into one group's completion counters would release the turn early or never)
+            if (groups[h].turn == s.turn && groups[h].turn_group == s.turn_group) {
+                lantern::set_error("commit turn-taking: groups %d and %d share `turn` and turn_group %d (one turn_group per group of a call; sharing a stream is fine)", h, g,
+                                   s.turn_group);
+                return fail(g, "turn", LANTERN_E_INVALID);
+            }
     }
     for (int g = 0; g < n_groups; ++g) {
         const lantern_step_group &s = groups[g];
@@ -128,7 +137,8 @@ extern "C" int lantern_verify_step(const lantern_step_group *groups, int n_group
                                           s.win_len, s.out_win, s.row_hot, s.out_kind, s.temperature, s.top_p, s.stream);
         if (rc) return fail(g, "cfg_mask_topk_window", rc);
     }
-    for (int g = 0; g < n_groups; ++g) {
+    // The walk and the commit of one group, as two launches on its stream.
+    auto walk = [&](int g) -> int {
         const lantern_step_group &s = groups[g];
         if (s.greedy) {
             const lantern_step_greedy &q = *s.greedy;
@@ -140,7 +150,7 @@ extern "C" int lantern_verify_step(const lantern_step_group *groups, int n_group
             rc = lantern_accept_gather(nullptr, 0, s.B, 1, s.N, 0, s.retrieve, 0, s.P, s.D, nullptr, s.ep_buf.best, s.ep_buf.accept_len, q.out_row, s.V, nullptr,
                                        nullptr, nullptr, q.token, s.stream);
             if (rc) return fail(g, "bonus argmax", rc);
-            continue;
+            return LANTERN_OK;
         }
         if (s.dense) {
             const lantern_step_dense &q = *s.dense;
@@ -154,7 +164,7 @@ extern "C" int lantern_verify_step(const lantern_step_group *groups, int n_group
                                            s.ep_buf.accept_len, q.sample_p, s.V, q.u_bonus, nullptr, nullptr, q.token, s.stream);
                 if (rc) return fail(g, "bonus draw", rc);
             }
-            continue;
+            return LANTERN_OK;
         }
         if (s.flags & LANTERN_STEP_FUSED_PREPARE) {          // candidates + listed rows + walk in ONE launch
             lantern::PrepArgs pa{};
@@ -167,7 +177,7 @@ extern "C" int lantern_verify_step(const lantern_step_group *groups, int n_group
             }
             rc = lantern::evaluate_posterior_window_fused(&s.ep, &s.ep_buf, &w, pa, s.row_ready, s.row_epoch, s.stream);
             if (rc) return fail(g, "evaluate_posterior (fused prepare)", rc);
-            continue;
+            return LANTERN_OK;
         }
         if (s.turn && !s.nodes && s.slab_ptrs) {          // commit turn-taking: the chain kernel ends when it is this group's turn to commit
             lantern_ep_window w = s.ep_win;
@@ -178,8 +188,9 @@ extern "C" int lantern_verify_step(const lantern_step_group *groups, int n_group
         rc = s.nodes ? lantern_evaluate_posterior_nodes(&s.ep, &s.ep_buf, &s.ep_win, s.nodes, s.stream)
                      : lantern_evaluate_posterior_window(&s.ep, &s.ep_buf, &s.ep_win, s.stream);
         if (rc) return fail(g, "evaluate_posterior", rc);
-    }
-    for (int g = 0; g < n_groups; ++g) {
+        return LANTERN_OK;
+    };
+    auto commit = [&](int g) -> int {
         const lantern_step_group &s = groups[g];
         if (!s.slab_ptrs) {
             if (s.turn) {          // (nothing would ever release the turn)
@@ -190,7 +201,7 @@ extern "C" int lantern_verify_step(const lantern_step_group *groups, int n_group
                 lantern::set_error("prepare_next rides in the commit launch: the group needs its KV slabs (slab_ptrs)");
                 return fail(g, "update_inference_inputs", LANTERN_E_INVALID);
             }
-            continue;
+            return LANTERN_OK;
         }
         // the next step's preparation in the same launch (prepare_next): its lengths are this step's + what this commit adds
         lantern::PrepArgs pa{};
@@ -218,6 +229,26 @@ extern "C" int lantern_verify_step(const lantern_step_group *groups, int n_group
                                                      s.ids_stride, s.ids_len, s.ids_buf ? (s.greedy ? s.greedy->token : (s.dense ? s.dense->token : s.ep_win.token)) : nullptr, prep,
                                                      s.turn ? &ta : nullptr);
         if (rc) return fail(g, "update_inference_inputs", rc);
+        return LANTERN_OK;
+    };
+    // Issue order.  A walk that takes a turn ends by waiting for turn[0] >= turn_wait, that is for commit launches with smaller tickets, and a hardware
+    // queue runs its packets in order -- so launches that wait are enqueued in the order of their tickets, each walk with its commit right behind it:
+    // over one call, and over successive calls whose tickets grow, every wait targets a launch that was enqueued EARLIER.  The earliest unfinished
+    // launch is then always at the head of its queue and can run, and no mapping of streams to hardware queues can make a wait outlast what it waits
+    // for -- several turn groups on one queue, or on one stream, included.  (Stage by stage -- all walks, then all commits -- two groups a < b that
+    // share a queue leave walk b in front of the commit a it waits for: every step then costs the wait's whole bound.)  The caller's array order is
+    // not relied on: ascending turn_wait, array order on ties.  Groups without `turn` wait for nothing and keep the stage-by-stage order.
+    std::vector<int> by_ticket;
+    for (int g = 0; g < n_groups; ++g)
+        if (groups[g].turn) by_ticket.push_back(g);
+    std::stable_sort(by_ticket.begin(), by_ticket.end(), [&](int a, int b) { return groups[a].turn_wait < groups[b].turn_wait; });
+    for (int g = 0; g < n_groups; ++g)
+        if (!groups[g].turn && (rc = walk(g))) return rc;
+    for (int g : by_ticket) {
+        if ((rc = walk(g))) return rc;
+        if ((rc = commit(g))) return rc;
     }
+    for (int g = 0; g < n_groups; ++g)
+        if (!groups[g].turn && (rc = commit(g))) return rc;
     return LANTERN_OK;
 }

@@ -16,8 +16,8 @@ This module is product-side host code: it never imports the oracle.
 from __future__ import annotations
 
 import ctypes as C
-import os
 import random
+import sys
 from dataclasses import dataclass
 from typing import List
 
@@ -43,23 +43,63 @@ HIDDEN = 4096
 
 
 
-_GROUP_STREAMS = {}
-_SKIPPED = []
+_GROUP_STREAMS = {}          # device -> {"drawn": streams taken from torch's pool, "distinct": those of them on hardware queues of their own}
+_POOL_STREAMS = 32           # torch hands out the same 32 streams per device round-robin
+
+
+def streams_share_queue(a, b) -> bool:
+    """Whether work on stream `b` has to wait for a kernel running on stream `a` (lantern_streams_share_queue: one hardware queue, or one stream)."""
+    shared = C.c_int(0)
+    check(_lib.lib().lantern_streams_share_queue(C.c_void_p(a.cuda_stream), C.c_void_p(b.cuda_stream), C.byref(shared)), "streams_share_queue")
+    return bool(shared.value)
 
 
 def group_streams(device, n: int):
-    """The stream-group streams of a device, created once per process and shared by every workload built after (workloads run one at a time): a
-    stream is bound to a hardware queue when it is created, and streams created late in a process that has made many land two groups on one
-    queue -- measured: a side configuration's step 46 -> 80 us in the third workload of a bench run."""
+    """The stream-group streams of a device, chosen once per process and shared by every workload built after (workloads run one at a time).  The
+    runtime binds a stream to one of a few hardware queues (GPU_MAX_HW_QUEUES of the caller's environment, 4 by default) and a queue runs its
+    packets in order: two groups on one queue run one after the other.  So streams are drawn from torch's pool and one is kept only if it shares a
+    queue with none already kept (streams_share_queue).  The current stream is idle inside the step loop and needs no queue of its own.  If the pool
+    cannot supply n such streams -- more groups than queues -- the first n drawn are used; group_streams_report() says which it was."""
     key = str(torch.device(device))
-    have = _GROUP_STREAMS.get(key)
-    if have is None:
-        have = _GROUP_STREAMS[key] = []
-        for _ in range(int(os.environ.get("LANTERN_GROUP_STREAM_SKIP", "0"))):          # tuning knob (diagnostic): start further along torch's stream pool
-            _SKIPPED.append(torch.cuda.Stream(device=device))
-    while len(have) < n:
-        have.append(torch.cuda.Stream(device=device))
-    return have[:n]
+    have = _GROUP_STREAMS.setdefault(key, {"drawn": [], "distinct": []})
+    drawn, distinct = have["drawn"], have["distinct"]
+    while len(distinct) < n and len(drawn) < _POOL_STREAMS:
+        st = torch.cuda.Stream(device=device)
+        if any(st.cuda_stream == d.cuda_stream for d in drawn):
+            break          # (the pool has come round)
+        drawn.append(st)
+        if not any(streams_share_queue(k, st) for k in distinct):
+            distinct.append(st)
+    if len(distinct) >= n:
+        have["last"] = dict(requested=n, distinct_queues=True, queues_found=len(distinct), drawn=len(drawn))
+        return distinct[:n]
+    while len(drawn) < n:
+        drawn.append(torch.cuda.Stream(device=device))
+    have["last"] = dict(requested=n, distinct_queues=False, queues_found=len(distinct), drawn=len(drawn))
+    return drawn[:n]
+
+
+def group_streams_report(device) -> dict:
+    """What the last group_streams(device, n) found: requested, distinct_queues (every group on a queue of its own), queues_found, drawn."""
+    return dict(_GROUP_STREAMS.get(str(torch.device(device)), {}).get("last", {}))
+
+
+def _turn_timeouts(wl) -> int:
+    """Workgroups of the chain kernel that gave up waiting for their commit turn since workload `wl` was built (lantern_step_group.turn, word 1):
+    0 in a healthy run.  Synchronises."""
+    if not hasattr(wl, "_turn"):
+        return 0
+    wl.sync()
+    return int(wl._turn[1].item())
+
+
+def _warn_turn_timeouts(wl):
+    """One warning per workload, not an error: the results are correct (the turn is scheduling), the step time is not what it should be."""
+    n = _turn_timeouts(wl)
+    if n and not getattr(wl, "_turn_warned", False):
+        wl._turn_warned = True
+        print(f"warning: {n} chain-kernel workgroups gave up waiting for their commit turn (2 ms each): the groups' launches did not take turns as issued; "
+              f"group streams: {group_streams_report(wl.device)}", file=sys.stderr)
 
 
 @dataclass
@@ -127,6 +167,8 @@ class WorkloadConfig:
     n_groups: int = 1               # >1: the sequences are split into groups, each launched on its own HIP stream, so that one
                                     # group's latency-bound evaluate_posterior overlaps the others' bandwidth-bound kernels
                                     # (independent sequences: no ordering between groups exists)
+    shared_stream: bool = False     # n_groups > 1: every group on ONE stream (what groups on one hardware queue amount to, without needing a machine
+                                    # that is short of queues): the groups run one after the other; with commit_window the turns must still never wait
 
 
 def build_neighbour_table(device, seed: int = 0) -> torch.Tensor:
@@ -344,7 +386,7 @@ class LuminaVerifyWorkload:
         self.st_token = torch.zeros(B, dtype=torch.int64, device=device)
         self.u_cur = torch.zeros(B, dtype=torch.float64, device=device)
         self.step_dev = torch.zeros(cfg.n_groups, dtype=torch.int64, device=device)    # one device step counter per group
-        self.streams = group_streams(device, cfg.n_groups) if cfg.n_groups > 1 else [None]
+        self.streams = (group_streams(device, 1) * cfg.n_groups if cfg.shared_stream else group_streams(device, cfg.n_groups)) if cfg.n_groups > 1 else [None]
         self.side = [torch.cuda.Stream(device=device) for _ in range(cfg.n_groups)] if cfg.side_stream else None
         self._ev = [[torch.cuda.Event() for _ in range(4)] for _ in range(cfg.n_groups)]
         self._L = _lib.lib()
@@ -1001,12 +1043,16 @@ class LuminaVerifyWorkload:
         moved = ((ret != t) & live).sum().item() * 2
         return float(2 * moved * per_pos)
 
+    def turn_timeouts(self) -> int:
+        return _turn_timeouts(self)
+
     def check_status(self, i0: int, i1: int):
         self.sync()
         st = self.log_cnt[i0:i1, :, 5]
         if int(st.abs().sum().item()) != 0:
             bad = torch.nonzero(st)[0].tolist()
             raise _lib.LanternError(f"evaluate_posterior status {int(st[bad[0], bad[1]])} at step {i0 + bad[0]} seq {bad[1]}")
+        _warn_turn_timeouts(self)
 
 
 # =====================================================================================================================
@@ -1372,3 +1418,7 @@ class DynamicVerifyWorkload:
         if int(stt.abs().sum().item()) != 0:
             bad = torch.nonzero(stt)[0].tolist()
             raise _lib.LanternError(f"evaluate_posterior status {int(stt[bad[0], bad[1]])} at step {i0 + bad[0]} seq {bad[1]}")
+        _warn_turn_timeouts(self)
+
+    def turn_timeouts(self) -> int:
+        return _turn_timeouts(self)
