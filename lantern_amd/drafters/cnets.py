@@ -205,15 +205,8 @@ class DraftPlan:
         expansion's outputs, positions(i) [2, T] or [T] int64 per depth as a [depth, ...] tensor -- or positions None and len_posi (an int, or a [B, 1] /
         [B] device tensor: the streams' lengths; depth i sits at len_posi + i; position_diff: the unconditional row's offset, cnets_anole.py:858-862)
         and head_len (the stream whose positions drive the Lumina grammar rows: the head sees head_len + i + 1), filled here with one launch each."""
-        a, B, T, D = self.args, self.B, self.T, self.depth
-        past = pkv[0][0].shape[2]
-        ks, vs = self.layer._cache_slab(B, self.nk, self.d, past + D * T, self.dev, pkv[0])
-        a.k_slab, a.v_slab, a.kv_rows = ks.data_ptr(), vs.data_ptr(), ks.shape[2]
-        self._slab, self.past = (ks, vs), past
-        need = int(self._L.lantern_tree_attention_workspace(B, self.nq, self.ROWS, self.d, self._C.c_int64(ks.shape[2])))
-        if self.ta is None or self.ta.numel() < need:
-            self.ta = torch.empty(max(need, 16), dtype=torch.uint8, device=self.dev)
-        a.ta_ws, a.ta_ws_bytes = self.ta.data_ptr(), self.ta.numel()
+        B, T, D = self.B, self.T, self.depth
+        self._bind(pkv, D * T, kv_start)
         # (hidden0 / ids0 may arrive as broadcast views -- `last_hidden[:, None].expand(B, T, H)`, `ids.reshape(1, T).expand(B, T)` -- and are materialised by
         # these copies, one launch each; parents[0] and the first T ancestor words are constants no depth writes: set once in __init__)
         self.hidden[0].copy_(hidden0)
@@ -232,6 +225,19 @@ class DraftPlan:
         elif head_len is not None:
             torch.add(self.steps1_row, head_len.reshape(()), out=self.head_pos)
             head_positions = self.head_pos
+        self._lumina_grammar = head_positions is not None
+
+    def _bind(self, pkv, tree_rows: int, kv_start):
+        """Every drafting call's start: the layer's slab behind the prefix cache `pkv` + `tree_rows` rows, the tree-attention workspace for it, kv_start, cfg."""
+        a, B = self.args, self.B
+        past = pkv[0][0].shape[2]
+        ks, vs = self.layer._cache_slab(B, self.nk, self.d, past + tree_rows, self.dev, pkv[0])
+        a.k_slab, a.v_slab, a.kv_rows = ks.data_ptr(), vs.data_ptr(), ks.shape[2]
+        self._slab, self.past = (ks, vs), past
+        need = int(self._L.lantern_tree_attention_workspace(B, self.nq, self.ROWS, self.d, self._C.c_int64(ks.shape[2])))
+        if self.ta is None or self.ta.numel() < need:
+            self.ta = torch.empty(max(need, 16), dtype=torch.uint8, device=self.dev)
+        a.ta_ws, a.ta_ws_bytes = self.ta.data_ptr(), self.ta.numel()
         if kv_start is None:
             if not self._kv_start_zero:
                 self.kv_start.zero_()
@@ -239,10 +245,7 @@ class DraftPlan:
         else:
             self.kv_start.copy_(kv_start)
             self._kv_start_zero = False
-        a.kv_start = self.kv_start.data_ptr()
-        a.positions_per_batch_row = 1
-        a.cfg = float(self.model.cfg_scale)
-        self._lumina_grammar = head_positions is not None
+        a.kv_start, a.positions_per_batch_row, a.cfg = self.kv_start.data_ptr(), 1, float(self.model.cfg_scale)
 
     def run(self, i: int):
         """Depth i: one C call."""
@@ -342,22 +345,7 @@ class StaticDraftPlan(DraftPlan):
         mdl = self.model
         self.parity ^= 1
         res = self.res[self.parity]
-        past = pkv[0][0].shape[2]
-        ks, vs = self.layer._cache_slab(B, self.nk, self.d, past + self.key_off[-1], self.dev, pkv[0])
-        a.k_slab, a.v_slab, a.kv_rows = ks.data_ptr(), vs.data_ptr(), ks.shape[2]
-        self._slab, self.past = (ks, vs), past
-        need = int(L.lantern_tree_attention_workspace(B, self.nq, self.ROWS, self.d, C.c_int64(ks.shape[2])))
-        if self.ta is None or self.ta.numel() < need:
-            self.ta = torch.empty(max(need, 16), dtype=torch.uint8, device=self.dev)
-        a.ta_ws, a.ta_ws_bytes = self.ta.data_ptr(), self.ta.numel()
-        if kv_start is None:
-            if not self._kv_start_zero:
-                self.kv_start.zero_()
-                self._kv_start_zero = True
-        else:
-            self.kv_start.copy_(kv_start)
-            self._kv_start_zero = False
-        a.kv_start, a.positions_per_batch_row, a.cfg = self.kv_start.data_ptr(), 1, float(mdl.cfg_scale)
+        self._bind(pkv, self.key_off[-1], kv_start)
         a.tree_bits = self.tree_bits.data_ptr()
         # the draws of this call: injected indices, injected uniforms, or fresh uniforms (ONE torch.rand per drafting call)
         idx = getattr(mdl, "static_draw_idx", None)
@@ -589,16 +577,9 @@ class Model(nn.Module):
         if hidden_states.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and H % 16 == 0:
             emb = self.embed_tokens.weight
             emb = emb if emb.dtype == torch.bfloat16 else emb.to(torch.bfloat16)
-            ids, hid = input_ids.reshape(-1), hidden_states.reshape(B * T, H)
-            fp8 = self.weight_format == "fp8"          # (fp8: every row count on the packed weight -- ops.drafter_fc)
-            pk = self._packed_weight("fc", w) if ((B * T <= 32 or fp8) and H % 64 == 0) else None          # the drafting shape streams the packed weight
+            pk = self._packed_weight("fc", w) if H % 64 == 0 else None          # (which rows read it: ops.drafter_gemm_route("input"))
             scale = float(self.embed_upscale) if self.embed_upscale > 1.0 else 1.0
-            if fp8 and B * T > 128:                            # an fp8 prefill: every row in one launch of the tiled kernel's gather form
-                return ops.drafter_fc(ids, hid, emb, w, self.fc.bias, embed_scale=scale, packed=pk).view(B, T, H)
-            out = torch.empty_like(hid)
-            for s in range(0, B * T, 128):                     # one drafter call is <= ~120 rows; bf16 prefills go in slices
-                out[s:s + 128] = ops.drafter_fc(ids[s:s + 128], hid[s:s + 128], emb, w, self.fc.bias, embed_scale=scale, packed=pk)
-            return out.view(B, T, H)
+            return ops.drafter_input_stage(input_ids.reshape(-1), hidden_states.reshape(B * T, H), emb, w, self.fc.bias, scale, pk).view(B, T, H)
         # other dtypes (f32 checkpoints in tests): the same arithmetic in torch on the device
         e = self.embed_tokens(input_ids).to(hidden_states.dtype)
         if self.embed_upscale > 1.0:

@@ -1,17 +1,18 @@
-"""The drafter's single decoder layer on the HIP skinny GEMM (second part).
+"""The drafter's single decoder layer, both kinds, on the HIP kernels.
 
-Reference: models/drafters/cnets_lumina_mgpt.py -- ChameleonDecoderLayer (:769-843) = ChameleonRMSNorm (:209-223) ->
-ChameleonAttention (:411-541: q/k/v projections, per-head ChameleonLayerNorm :375-396, rotary :228-357, KV concat, eager
-softmax attention under the additive drafter mask, o_proj) -> residual -> ChameleonRMSNorm -> ChameleonMLP (:359-373) -> residual.
+Reference: models/drafters/cnets_lumina_mgpt.py -- ChameleonDecoderLayer (:769-843) = ChameleonRMSNorm (:209-223) -> ChameleonAttention (:411-541: q/k/v
+projections, per-head ChameleonLayerNorm :375-396, rotary :228-357, KV concat, eager softmax attention under the additive drafter mask, o_proj) ->
+residual -> ChameleonRMSNorm -> ChameleonMLP (:359-373) -> residual; models/drafters/cnets_llamagen.py -- LlamaDecoderLayer (:428-494: no input norm
+in layer 0, no per-head norm, pair rotary from `freqs_cis`).
 
-During drafting the layer sees M = 2 x top_k = 20 rows per call, six calls per verify cycle: its cost is the 404 MB of
-projection weights it streams (7B: 4 x 4096^2 + 3 x 4096 x 11008 bf16), not arithmetic.  The seven projections therefore go
-through `lantern_linear_rows` (drafter_fc.hip: `linear_rows_kernel`, MFMA 32x32x16 fed straight from the [out, in] weight rows,
-M <= 128) with q/k/v and gate/up each fused into ONE launch over a concatenated weight; norms, head norm + rotary are single HIP kernels and
-the attention is lantern_tree_attention when the caller hands the tree block over as ancestor words (cnets.Model.forward does).  CPU tensors
-and other dtypes (the f32 reference vectors) and M > 128 (the drafter's prefill) take torch.nn.functional.linear; the drafting shape on the
-device either runs the fused HIP path or raises (no silent switch) -- the layer is a drop-in nn.Module with the reference's parameter names
-(`self_attn.q_proj.weight`, `mlp.gate_proj.weight`, `input_layernorm.weight`, ...), so a reference drafter checkpoint loads into it unchanged.
+`DecoderLayer` (Lumina-mGPT, Anole) and `LlamaDecoderLayer` (LlamaGen) are drop-in nn.Modules with the reference's parameter names and call
+signatures: a reference drafter checkpoint loads unchanged.  bf16 device tensors take ONE fused body, `DecoderLayer._fast`: rmsnorm, the fused q/k/v
+GEMM, the head stage (the kinds differ here and in the input norm only: `_head_stage`, `_input_norm`), the cache append (a layer-owned slab that grows
+in place, or torch.cat), attention (`_attend`: ancestor words, block-causal, or an additive mask restated as words -- always lantern_tree_attention),
+o_proj + residual, rmsnorm, gate/up with silu * up in the epilogue, down_proj + residual.  The four GEMMs read packed weights (`weight_format`: bf16
+or fp8) through ops.drafter_linear; which kernel that is at a given row count (stream-K up to the 32 rows of the drafting shape, the row-blocked /
+tiled kernels for a prefill) is said once, in ops.drafter_gemm_route.  A drafting-shape call that misses a precondition of the fused body raises (no
+silent switch).  CPU tensors and f32 (the reference vectors) take the torch composition, per projection through `skinny_linear`.
 """
 from __future__ import annotations
 
@@ -42,15 +43,6 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     return F.linear(x, weight, bias)          # f32 / CPU: the composition the golden vectors are checked on
 
 
-def _mm(A, weight, epilogue: int = 0, **kw):
-    """The layer's GEMMs on the packed weights: the stream-K kernel at the drafting shape (<= 32 rows), the row-blocked one for prefills."""
-    if A.shape[0] <= 32:
-        return ops.linear_rows_streamk(A, weight, epilogue, **kw)
-    kw.pop("pair_rows", None)
-    return ops.linear_rows_packed(A, weight, epilogue, **kw)
-
-
-
 def additive_mask_words(attention_mask, B: int, T: int, S: int):
     """An additive attention mask [1|B, 1, T, >= S] (0 = visible, finfo.min = hidden: what _prepare_decoder_attention_mask builds) restated as the
     HIP kernels' description of visibility: one first-visible-key index per batch row for the S - T cached keys (left padding) + one ancestor
@@ -75,12 +67,24 @@ def additive_mask_words(attention_mask, B: int, T: int, S: int):
     return ok, kv_start, words
 
 
-def _attend_without_tree(q, k, v, attention_mask, kv_start, past, T, B, H, nq, nk):
-    """The branch of the fused layers for callers that bring neither ancestor words nor the causal hint (cnets.Model.forward always brings
-    one).  Still the HIP attention, never torch's SDPA: no mask = every new token sees every key; an additive mask is restated as
-    ancestor words + a first-visible-key index (additive_mask_words; one host read to check that it can be) for T <= 64 new tokens, and
-    refused where it cannot."""
+def _attend(q, k, v, attention_mask, kv_start, past, tree_bits, tree_keys, causal):
+    """The fused layer's attention, q [B, nq, T, d] against k / v [B, nk, past + T, d] -> [B * T, nq * d]: the tree block as ancestor words, else a
+    causal prefill block by block, else (no hint; cnets.Model.forward always brings one) what the additive mask says: none = every new token sees every
+    key; a mask is restated as ancestor words + a first-visible-key index (additive_mask_words; one host read) for T <= 64 new tokens, or refused.
+    lantern_tree_attention every time: no [T, S] scores, no repeat_kv, no SDPA."""
+    B, nq, T, d = q.shape
     S = past + T
+    if tree_bits is not None:
+        # the T new tokens are the last T of the `tree_keys` tree keys; the kernel takes as many query rows as tree keys: the
+        # rows in front are placeholders (zero queries that see themselves)
+        t1 = int(tree_keys)
+        qp = q.transpose(1, 2)                                  # [B, T, nq, d]
+        if t1 > T:
+            qp = torch.zeros((B, t1, nq, d), dtype=q.dtype, device=q.device)
+            qp[:, t1 - T:] = q.transpose(1, 2)
+        return ops.tree_attention(qp, k, v, tree_bits, kv_start=kv_start, max_kv_len=S)[:, t1 - T:].reshape(B * T, nq * d)
+    if causal:
+        return causal_block_attention(q, k, v, kv_start, past).reshape(B * T, nq * d)
     if T > 64:
         raise ops._lib.LanternError(
             f"DecoderLayer (fused HIP path): {T} new tokens with an additive mask and no `causal=True` hint: tree attention takes at most 64 query rows -- "
@@ -94,7 +98,8 @@ def _attend_without_tree(q, k, v, attention_mask, kv_start, past, T, B, H, nq, n
                 "DecoderLayer (fused HIP path): this additive attention_mask is not (left padding) x (a block over the new tokens): no HIP kernel "
                 "describes it -- set layer.fused = False for the torch composition")
         kv_start = start if kv_start is None else kv_start
-    return ops.tree_attention(q.transpose(1, 2), k, v, words, kv_start=kv_start, max_kv_len=S).reshape(B * T, H)
+    return ops.tree_attention(q.transpose(1, 2), k, v, words, kv_start=kv_start, max_kv_len=S).reshape(B * T, nq * d)
+
 
 _CAUSAL_WORDS = {}
 
@@ -356,57 +361,65 @@ class DecoderLayer(nn.Module):
         self.repack()
         return super()._load_from_state_dict(*a, **k)
 
-    def _fast(self, x, attention_mask, position_ids, past_key_value, use_cache, tree_bits=None, tree_keys=0, kv_start=None, causal=False):
-        """Decode shape on the device (<= 32 bf16 rows): rmsnorm, fused q/k/v GEMM, head norm + rotary (+ cache append), one attention call,
-        o_proj + residual, rmsnorm, gate/up GEMM with silu * up in its epilogue, down_proj + residual -- the four GEMMs in stream-K form
-        (lantern_linear_rows_streamk: one launch each, the weight split into equal contiguous shares over 2 workgroups per CU).
-        With `tree_bits` (ops.drafter_tree_bits: the tree block of the drafter's mask as ancestor words) the attention is
-        lantern_tree_attention over the cache in place -- no additive mask, no repeat_kv, no [T, S] scores."""
+    def _input_norm(self, x2):
+        return ops.rmsnorm_rows(x2, self.input_layernorm.weight, self.input_layernorm.variance_epsilon)
+
+    def _head_stage(self, qkv, B, T, past, position_ids, **slab):
+        """qkv [B * T, (nq + 2 nk) d] -> (q, k, v) [B, heads, T, d]: per-head layer norm + rotary at `position_ids` in one kernel; with `slab`
+        (k_slab, v_slab, row0) k / v are written there and not returned."""
+        at = self.self_attn
+        cos, sin = at.rotary_emb.tables_bf16(qkv.device, past + T)
+        return ops.qk_norm_rope(qkv, B, T, at.num_heads, at.num_key_value_heads, at.head_dim, at.q_norm.weight, at.q_norm.bias, at.k_norm.weight, at.k_norm.bias,
+                                cos, sin, position_ids, **slab)
+
+    def _fast(self, x, attention_mask, rotary, past_key_value, use_cache, tree_bits=None, tree_keys=0, kv_start=None, causal=False):
+        """The fused body, for both layer kinds (`rotary`: what the kind's head stage turns by -- position_ids here, freqs_cis rows for LlamaGen):
+        rmsnorm, fused q/k/v GEMM, head stage (+ cache append), one attention call, o_proj + residual, rmsnorm, gate/up GEMM with silu * up in
+        its epilogue, down_proj + residual.  With `tree_bits` (ops.drafter_tree_bits: the tree block of the drafter's mask as ancestor words) the
+        attention runs over the cache in place."""
         at, mlp = self.self_attn, self.mlp
         B, T, H = x.shape
-        nq, nk, d = at.num_heads, at.num_key_value_heads, at.head_dim
         x2 = x.reshape(B * T, H)
-        xn = ops.rmsnorm_rows(x2, self.input_layernorm.weight, self.input_layernorm.variance_epsilon)
         wq, b = self._packed_fused("qkv", (at.q_proj, at.k_proj, at.v_proj))
-        qkv = _mm(xn, wq, bias=b)          # stream-K: every workgroup streams an equal, contiguous share of the weight (prefills: row blocks)
-        kv_len = T + (past_key_value[0].shape[-2] if past_key_value is not None else 0)
-        cos, sin = at.rotary_emb.tables_bf16(x.device, kv_len)
+        qkv = ops.drafter_linear(self._input_norm(x2), wq, bias=b)
         past = 0 if past_key_value is None else past_key_value[0].shape[-2]
+        kv_len = past + T
         if self.inplace_cache and use_cache:
             # the cache lives in a slab of this layer and grows in place: `present` is a view of it; a `past` that is such a view (what the
             # drafter hands back: the previous call's present, or a shorter prefix of it after a rollback) costs no copy at all
-            ks, vs = self._cache_slab(B, nk, d, kv_len, x.device, past_key_value)
-            q, _, _ = ops.qk_norm_rope(qkv, B, T, nq, nk, d, at.q_norm.weight, at.q_norm.bias, at.k_norm.weight, at.k_norm.bias, cos, sin, position_ids,
-                                       k_slab=ks, v_slab=vs, row0=past)
+            ks, vs = self._cache_slab(B, at.num_key_value_heads, at.head_dim, kv_len, x.device, past_key_value)
+            q, _, _ = self._head_stage(qkv, B, T, past, rotary, k_slab=ks, v_slab=vs, row0=past)
             k, v = ks[:, :, :kv_len], vs[:, :, :kv_len]
         else:
-            q, k, v = ops.qk_norm_rope(qkv, B, T, nq, nk, d, at.q_norm.weight, at.q_norm.bias, at.k_norm.weight, at.k_norm.bias, cos, sin, position_ids)
+            q, k, v = self._head_stage(qkv, B, T, past, rotary)
             if past_key_value is not None:
                 k, v = torch.cat([past_key_value[0], k], dim=2), torch.cat([past_key_value[1], v], dim=2)
-        present = (k, v) if use_cache else None
-        if tree_bits is not None:
-            # the T new tokens are the last T of the `tree_keys` tree keys; the kernel takes as many query rows as tree keys: the
-            # rows in front are placeholders (zero queries that see themselves)
-            t1 = int(tree_keys)
-            qn = q.transpose(1, 2)                                  # [B, T, nq, d]
-            if t1 > T:
-                qp = torch.zeros((B, t1, nq, d), dtype=q.dtype, device=q.device)
-                qp[:, t1 - T:] = qn
-            else:
-                qp = qn
-            o = ops.tree_attention(qp, k, v, tree_bits, kv_start=kv_start, max_kv_len=kv_len)[:, t1 - T:].reshape(B * T, H)
-        elif causal:
-            # a prefill: causal among the new tokens behind the left padding, block by block on the same kernel (no [T, S] mask, no eager softmax)
-            o = causal_block_attention(q, k, v, kv_start, past).reshape(B * T, H)
-        else:
-            o = _attend_without_tree(q, k, v, attention_mask, kv_start, past, T, B, H, nq, nk)
-        h1 = _mm(o, self._packed("o", at.o_proj.weight), ops.EPI_RESIDUAL, bias=at.o_proj.bias, residual=x2)
+        o = _attend(q, k, v, attention_mask, kv_start, past, tree_bits, tree_keys, causal)
+        h1 = ops.drafter_linear(o, self._packed("o", at.o_proj.weight), ops.EPI_RESIDUAL, bias=at.o_proj.bias, residual=x2)
         hn = ops.rmsnorm_rows(h1, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon)
         inter = mlp.gate_proj.out_features
         wg, bg = self._packed_fused("gate_up", (mlp.gate_proj, mlp.up_proj), inter)
-        act = _mm(hn, wg, ops.EPI_SILU_MUL, bias=bg, pair_rows=inter)
-        out = _mm(act, self._packed("down", mlp.down_proj.weight), ops.EPI_RESIDUAL, bias=mlp.down_proj.bias, residual=h1)
-        return out.reshape(B, T, H), present
+        act = ops.drafter_linear(hn, wg, ops.EPI_SILU_MUL, bias=bg, pair_rows=inter)
+        out = ops.drafter_linear(act, self._packed("down", mlp.down_proj.weight), ops.EPI_RESIDUAL, bias=mlp.down_proj.bias, residual=h1)
+        return out.reshape(B, T, H), ((k, v) if use_cache else None)
+
+    def _run_fast(self, x, attention_mask, rotary, past_key_value, use_cache, tree_bits, tree_keys, kv_start, causal):
+        if tree_bits is not None and not (0 < x.shape[1] <= tree_keys <= 64):
+            tree_bits = None
+        y, present = self._fast(x, attention_mask, rotary, past_key_value, use_cache, tree_bits, tree_keys, kv_start, causal and tree_bits is None)
+        return (y, present) if use_cache else (y,)
+
+    def _run_torch(self, hidden_states, output_attentions, use_cache, **attn_kw):
+        self._no_quiet_bf16()
+        x = self.input_layernorm(hidden_states) if hasattr(self, "input_layernorm") else hidden_states
+        a, w, present = self.self_attn(x, output_attentions=output_attentions, use_cache=use_cache, **attn_kw)
+        hidden_states = hidden_states + a
+        hidden_states = hidden_states + self.mlp(self.post_attention_layernorm(hidden_states))
+        return (hidden_states,) + ((w,) if output_attentions else ()) + ((present,) if use_cache else ())
+
+    def _drafting_shape(self, x, output_attentions):          # <= 32 bf16 rows on the device: the fused body must run them or raise
+        return (self.fused and not output_attentions and x.dim() == 3 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[0] * x.shape[1] <= 32
+                and _hip_ok(x, self.self_attn.q_proj.weight))
 
     def _fast_ok(self, x, position_ids, output_attentions, causal=False):
         at = self.self_attn
@@ -449,32 +462,15 @@ class DecoderLayer(nn.Module):
 
     def forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_value=None, output_attentions=False, use_cache=False,
                 tree_bits=None, tree_keys=0, kv_start=None, causal=False, **kw) -> Tuple[torch.Tensor, ...]:
-        if (self.fused and not output_attentions and hidden_states.dim() == 3 and hidden_states.is_cuda and hidden_states.dtype == torch.bfloat16
-                and hidden_states.shape[0] * hidden_states.shape[1] <= 32 and _hip_ok(hidden_states, self.self_attn.q_proj.weight)
-                and not self._fast_ok(hidden_states, position_ids, output_attentions)):
+        if self._drafting_shape(hidden_states, output_attentions) and not self._fast_ok(hidden_states, position_ids, output_attentions):
             # the drafting shape must not slide onto torch's ops unnoticed: say which precondition of the fused HIP path is missing
-            at = self.self_attn
             raise ops._lib.LanternError(
                 f"DecoderLayer: the drafting shape ({tuple(hidden_states.shape)}, bf16, device) takes the fused HIP path, which needs head_dim 64 or 128 "
-                f"(got {at.head_dim}), silu, bf16 weights / norms, hidden % 16 == 0 and position_ids; set `layer.fused = False` for the per-projection "
+                f"(got {self.self_attn.head_dim}), silu, bf16 weights / norms, hidden % 16 == 0 and position_ids; set `layer.fused = False` for the per-projection "
                 "path (skinny GEMM under torch's element-wise ops)")
         if self._fast_ok(hidden_states, position_ids, output_attentions, causal):
-            if tree_bits is not None and not (0 < hidden_states.shape[1] <= tree_keys <= 64):
-                tree_bits = None
-            y, present = self._fast(hidden_states, attention_mask, position_ids, past_key_value, use_cache, tree_bits, tree_keys, kv_start,
-                                    causal and tree_bits is None)
-            return (y, present) if use_cache else (y,)
-        self._no_quiet_bf16()
-        a, w, present = self.self_attn(self.input_layernorm(hidden_states), attention_mask=attention_mask, position_ids=position_ids,
-                                       past_key_value=past_key_value, output_attentions=output_attentions, use_cache=use_cache)
-        hidden_states = hidden_states + a
-        hidden_states = hidden_states + self.mlp(self.post_attention_layernorm(hidden_states))
-        out = (hidden_states,)
-        if output_attentions:
-            out += (w,)
-        if use_cache:
-            out += (present,)
-        return out
+            return self._run_fast(hidden_states, attention_mask, position_ids, past_key_value, use_cache, tree_bits, tree_keys, kv_start, causal)
+        return self._run_torch(hidden_states, output_attentions, use_cache, attention_mask=attention_mask, position_ids=position_ids, past_key_value=past_key_value)
 
 
 # ----------------------------------------------------------------------------- the LlamaGen drafter's layer
@@ -546,10 +542,8 @@ class LlamaAttention(nn.Module):
 class LlamaDecoderLayer(DecoderLayer):
     """Drop-in for the reference's LlamaDecoderLayer in the LlamaGen drafter (cnets_llamagen.py:428-494; same call signature incl. `freqs_cis`,
     same return tuple, same parameter names -- `self_attn.q_proj.weight`, `mlp.gate_proj.weight`, `post_attention_layernorm.weight`, and
-    `input_layernorm.weight` for index != 0: EAGLE drops layer 0's input norm).  At the drafting shape on the device (<= 32 bf16 rows, head_dim 64 or
-    128, hidden % 64 == 0) it runs the same HIP kernels as the Chameleon layer -- stream-K GEMMs on packed weights with the residual / silu * up
-    epilogues, lantern_rmsnorm_rows, lantern_tree_attention -- with lantern_qk_rope_pairs as the head stage (no per-head norm, pair rotary from the
-    gathered `freqs_cis` rows)."""
+    `input_layernorm.weight` for index != 0: EAGLE drops layer 0's input norm).  It runs DecoderLayer's fused body (needs hidden % 64 == 0) with
+    lantern_qk_rope_pairs as the head stage (no per-head norm, pair rotary from the gathered `freqs_cis` rows)."""
 
     def __init__(self, config, index: int = 0):
         nn.Module.__init__(self)
@@ -570,76 +564,26 @@ class LlamaDecoderLayer(DecoderLayer):
                 and at.head_dim in (64, 128) and x.shape[-1] % 64 == 0 and freqs_cis is not None and self.mlp.act_fn is F.silu
                 and self.post_attention_layernorm.weight.dtype == torch.bfloat16)
 
-    def _fast(self, x, attention_mask, freqs_cis, past_key_value, use_cache, tree_bits=None, tree_keys=0, kv_start=None, causal=False):
-        at, mlp = self.self_attn, self.mlp
-        B, T, H = x.shape
-        nq, nk, d = at.num_heads, at.num_key_value_heads, at.head_dim
-        x2 = x.reshape(B * T, H)
-        xn = x2 if self.index == 0 else ops.rmsnorm_rows(x2, self.input_layernorm.weight, self.input_layernorm.variance_epsilon)
-        wq, b = self._packed_fused("qkv", (at.q_proj, at.k_proj, at.v_proj))
-        qkv = _mm(xn, wq, bias=b)
-        past = 0 if past_key_value is None else past_key_value[0].shape[-2]
-        kv_len = T + past
-        fr = freqs_cis.reshape(-1, d // 2, 2)                      # the reference hands over the rows of its table at this call's positions: [T, d/2, 2]
+    def _input_norm(self, x2):
+        return x2 if self.index == 0 else super()._input_norm(x2)
+
+    def _head_stage(self, qkv, B, T, past, freqs_cis, **slab):
+        at = self.self_attn
+        fr = freqs_cis.reshape(-1, at.head_dim // 2, 2)                      # the reference hands over the rows of its table at this call's positions: [T, d/2, 2]
         pos = self.__dict__.get("_arange")
-        if pos is None or pos.numel() < fr.shape[0] or pos.device != x.device:
-            pos = self.__dict__["_arange"] = torch.arange(max(64, fr.shape[0]), dtype=torch.int64, device=x.device)
+        if pos is None or pos.numel() < fr.shape[0] or pos.device != qkv.device:
+            pos = self.__dict__["_arange"] = torch.arange(max(64, fr.shape[0]), dtype=torch.int64, device=qkv.device)
         if fr.shape[0] not in (T, B * T):
             raise ops._lib.LanternError(f"LlamaDecoderLayer: freqs_cis holds {fr.shape[0]} rows for {T} tokens")
-        if self.inplace_cache and use_cache:
-            ks, vs = self._cache_slab(B, nk, d, kv_len, x.device, past_key_value)
-            q, _, _ = ops.qk_rope_pairs(qkv, B, T, nq, nk, d, fr, pos[:fr.shape[0]], k_slab=ks, v_slab=vs, row0=past)
-            k, v = ks[:, :, :kv_len], vs[:, :, :kv_len]
-        else:
-            q, k, v = ops.qk_rope_pairs(qkv, B, T, nq, nk, d, fr, pos[:fr.shape[0]])
-            if past_key_value is not None:
-                k, v = torch.cat([past_key_value[0], k], dim=2), torch.cat([past_key_value[1], v], dim=2)
-        present = (k, v) if use_cache else None
-        if tree_bits is not None:
-            t1 = int(tree_keys)
-            qn = q.transpose(1, 2)
-            if t1 > T:
-                qp = torch.zeros((B, t1, nq, d), dtype=q.dtype, device=q.device)
-                qp[:, t1 - T:] = qn
-            else:
-                qp = qn
-            o = ops.tree_attention(qp, k, v, tree_bits, kv_start=kv_start, max_kv_len=kv_len)[:, t1 - T:].reshape(B * T, H)
-        elif causal:
-            o = causal_block_attention(q, k, v, kv_start, past).reshape(B * T, H)
-        else:
-            o = _attend_without_tree(q, k, v, attention_mask, kv_start, past, T, B, H, nq, nk)
-        h1 = _mm(o, self._packed("o", at.o_proj.weight), ops.EPI_RESIDUAL, residual=x2)
-        hn = ops.rmsnorm_rows(h1, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon)
-        inter = mlp.gate_proj.out_features
-        wg, bg = self._packed_fused("gate_up", (mlp.gate_proj, mlp.up_proj), inter)
-        act = _mm(hn, wg, ops.EPI_SILU_MUL, bias=bg, pair_rows=inter)
-        out = _mm(act, self._packed("down", mlp.down_proj.weight), ops.EPI_RESIDUAL, bias=mlp.down_proj.bias, residual=h1)
-        return out.reshape(B, T, H), present
+        return ops.qk_rope_pairs(qkv, B, T, at.num_heads, at.num_key_value_heads, at.head_dim, fr, pos[:fr.shape[0]], **slab)
 
     def forward(self, hidden_states, attention_mask=None, position_ids=None, freqs_cis=None, past_key_value=None, output_attentions=False,
                 use_cache=False, tree_bits=None, tree_keys=0, kv_start=None, causal=False, **kw) -> Tuple[torch.Tensor, ...]:
         if self._fast_ok(hidden_states, position_ids, output_attentions, freqs_cis, causal):
-            if tree_bits is not None and not (0 < hidden_states.shape[1] <= tree_keys <= 64):
-                tree_bits = None
-            y, present = self._fast(hidden_states, attention_mask, freqs_cis, past_key_value, use_cache, tree_bits, tree_keys, kv_start,
-                                    causal and tree_bits is None)
-            return (y, present) if use_cache else (y,)
-        if (self.fused and not output_attentions and hidden_states.dim() == 3 and hidden_states.is_cuda and hidden_states.dtype == torch.bfloat16
-                and hidden_states.shape[0] * hidden_states.shape[1] <= 32 and _hip_ok(hidden_states, self.self_attn.q_proj.weight)):
-            at = self.self_attn
+            return self._run_fast(hidden_states, attention_mask, freqs_cis, past_key_value, use_cache, tree_bits, tree_keys, kv_start, causal)
+        if self._drafting_shape(hidden_states, output_attentions):
             raise ops._lib.LanternError(
                 f"LlamaDecoderLayer: the drafting shape ({tuple(hidden_states.shape)}, bf16, device) takes the fused HIP path, which needs head_dim 64 or "
-                f"128 (got {at.head_dim}), hidden % 64 == 0, silu, bf16 weights / norms and freqs_cis; set `layer.fused = False` for torch's ops")
-        self._no_quiet_bf16()
-        residual = hidden_states
-        x = hidden_states if self.index == 0 else self.input_layernorm(hidden_states)
-        a, w, present = self.self_attn(x, attention_mask=attention_mask, position_ids=position_ids, freqs_cis=freqs_cis, past_key_value=past_key_value,
-                                       output_attentions=output_attentions, use_cache=use_cache)
-        hidden_states = residual + a
-        hidden_states = hidden_states + self.mlp(self.post_attention_layernorm(hidden_states))
-        out = (hidden_states,)
-        if output_attentions:
-            out += (w,)
-        if use_cache:
-            out += (present,)
-        return out
+                f"128 (got {self.self_attn.head_dim}), hidden % 64 == 0, silu, bf16 weights / norms and freqs_cis; set `layer.fused = False` for torch's ops")
+        return self._run_torch(hidden_states, output_attentions, use_cache, attention_mask=attention_mask, position_ids=position_ids, freqs_cis=freqs_cis,
+                               past_key_value=past_key_value)

@@ -692,6 +692,50 @@ def _packed_code(packed) -> int:
     return 0 if packed is None else packed.code
 
 
+W_ROWS, W_PACKED, W_FP8 = "row-major bf16", "packed bf16", "packed fp8"          # the weight forms of drafter_gemm_route
+
+
+def _weight_form(weight) -> str:
+    return (W_FP8 if weight.fmt == "fp8" else W_PACKED) if isinstance(weight, PackedLinearWeight) else W_ROWS
+
+
+def drafter_gemm_route(stage: str, M: int, weight: str, aligned: bool, tiled_from):
+    """Which kernels run a GEMM of the drafter on M rows: the (kernel, row0, rows) pieces, in launch order, that tile [0, M).  Pure (no torch, no library):
+    the ONE statement of the routing, executed by linear_rows_packed, drafter_fc / drafter_input_stage and drafter_linear.  `weight`: W_ROWS | W_PACKED |
+    W_FP8 (packed only where K % 64 == 0); `aligned`: K % 64 == 0 (input stage: H % 64 == 0); `tiled_from`: the "gemm_tiled_from" tuning value (default
+    129), or a function returning it, called only where the route depends on it (an fp8 weight outside the drafting shape).  Kernels go by their C entry; "/row-major" marks the input stage's stream-K entry reading the [H, 2H] nn.Linear weight, not the packed one.
+    stage "layer" (drafter_linear: the decoder layer's four GEMMs): up to 32 rows ONE stream-K launch on any weight form (M = 0 included); above, the
+      pieces of stage "packed" (the layer only keeps K % 64 != 0 weights row-major, and only reaches them at <= 32 rows).
+    stage "packed" (linear_rows_packed called by itself, any M): bf16 -> one linear_rows_packed (the C side picks row-blocked or tiled; it refuses a row-major weight);
+      fp8 -> below `tiled_from` stream-K blocks of 32 rows (the last one shorter; none at all for M = 0), from there one lantern_linear_rows_packed_fmt.
+    stage "input" (fc(cat(embed[ids], hidden))): up to 32 rows with H % 64 == 0 the stream-K entry on the weight the call has (packed if any), with
+      H % 64 != 0 (bf16 only) lantern_drafter_fc on the row-major weight.  Above 32 rows, bf16: slices of 128 rows on lantern_drafter_fc, row-major --
+      fp8: stream-K blocks of 32 below `tiled_from`, one lantern_drafter_fc_packed from there.
+      KNOWN ODDITY, kept because changing it changes bits (stream-K and the per-tile kernel sum in different orders), for a later change to settle: a
+      bf16 tail slice of <= 32 rows with H % 64 == 0 runs on stream-K with the ROW-MAJOR weight (150 rows = 128 on lantern_drafter_fc + 22 on stream-K)."""
+    if stage not in ("layer", "packed", "input") or weight not in (W_ROWS, W_PACKED, W_FP8) or M < 0 or (weight != W_ROWS and not aligned):
+        raise ValueError(f"drafter_gemm_route: stage {stage!r}, weight {weight!r} (packed: K % 64 == 0), M = {M}, aligned = {aligned}")
+
+    def blocks(kernel, size):
+        return [(kernel, r, min(size, M - r)) for r in range(0, M, size)]
+    if stage == "input":
+        sk = "drafter_fc_streamk/row-major" if weight == W_ROWS else "drafter_fc_streamk"
+        if M <= 32:
+            return [(sk if aligned else "drafter_fc", 0, M)]
+        if weight == W_FP8:
+            return blocks(sk, 32) if M < (tiled_from() if callable(tiled_from) else tiled_from) else [("drafter_fc_packed", 0, M)]
+        return [("drafter_fc_streamk/row-major" if n <= 32 and aligned else "drafter_fc", r, n) for _, r, n in blocks("", 128)]
+    if stage == "layer" and M <= 32:
+        return [("linear_rows_streamk", 0, M)]
+    if weight != W_FP8:
+        return [("linear_rows_packed", 0, M)]
+    return blocks("linear_rows_streamk", 32) if M < (tiled_from() if callable(tiled_from) else tiled_from) else [("linear_rows_packed_fmt", 0, M)]
+
+
+def _tiled_from() -> int:
+    return _lib.get_tuning("gemm_tiled_from")
+
+
 def pack_linear_weight(weight, pair_rows: int = 0, fmt: str = "bf16") -> PackedLinearWeight:
     """weight [N, K] bf16 (K % 64 == 0) -> PackedLinearWeight; pair_rows > 0: weight = cat(gate, up) rows, N = 2 * pair_rows.
     fmt = "fp8": quantised on the device to e4m3fn with a per-row f32 scale (s = max|row| / 448)."""
@@ -727,11 +771,11 @@ def unpack_linear_weight_fp8(packed: PackedLinearWeight):
     return q, scale
 
 
-def linear_rows_streamk(A, weight, epilogue: int = 0, n_rows: Optional[int] = None, bias=None, residual=None, pair_rows: int = 0, row_lo: int = 0):
+def linear_rows_streamk(A, weight, epilogue: int = 0, n_rows: Optional[int] = None, bias=None, residual=None, pair_rows: int = 0, row_lo: int = 0, out=None):
     """A [M <= 32, K] bf16 @ weight[row_lo : row_lo + n_rows].T in stream-K form (one launch, every workgroup streams an equal share of the
     weight): epilogue 0 (+ bias), EPI_RESIDUAL (+ residual [M, n_rows], torch's two roundings), EPI_SILU_MUL (weight = cat(gate, up) rows,
     pair_rows = distance gate -> up row: silu(gate) * up).  `weight`: the [N, K] tensor, or its PackedLinearWeight (the fast form).  The
-    workspace (partial tiles + tile counters, zeroed once) is kept per device and current stream."""
+    workspace (partial tiles + tile counters, zeroed once) is kept per device and current stream.  `out`: a contiguous [M, n_rows] bf16 tensor to write."""
     packed = isinstance(weight, PackedLinearWeight)
     if not A.is_cuda or A.dtype != torch.bfloat16:
         raise _lib.LanternError("linear_rows_streamk: A must be a bf16 device tensor")
@@ -749,7 +793,9 @@ def linear_rows_streamk(A, weight, epilogue: int = 0, n_rows: Optional[int] = No
             n_rows = pair_rows if epilogue == EPI_SILU_MUL else wt.shape[0] - row_lo
     L = _lib.lib()
     ws = _sk_workspace(A.device)
-    out = torch.empty((M, n_rows), dtype=torch.bfloat16, device=A.device)
+    if out is None:
+        out = torch.empty((M, n_rows), dtype=torch.bfloat16, device=A.device)
+    assert out.shape == (M, n_rows) and out.dtype == torch.bfloat16 and out.is_contiguous()
     r = None if residual is None else residual.contiguous()
     b = None if bias is None else bias.contiguous()
     check(L.lantern_linear_rows_streamk(C.c_void_p(A.data_ptr()), C.c_void_p(wt.data_ptr()), C.c_void_p(_ptr(b)), M, K, row_lo, n_rows,
@@ -758,10 +804,10 @@ def linear_rows_streamk(A, weight, epilogue: int = 0, n_rows: Optional[int] = No
     return out
 
 
-def linear_rows_packed(A, weight: "PackedLinearWeight", epilogue: int = 0, bias=None, residual=None):
-    """A [M, K] bf16 (ANY number of rows: the drafter's prompt prefill) @ the packed weight, epilogues as linear_rows_streamk
-    (lantern_linear_rows_packed: row blocks of 128 -- 64 for a gate / up pair -- re-stream the weight tile).  An fp8 weight: from "gemm_tiled_from" rows
-    (default 129) one launch of the tiled fp8 kernel (lantern_linear_rows_packed_fmt), below that the stream-K kernel in blocks of 32 rows."""
+def linear_rows_packed(A, weight: "PackedLinearWeight", epilogue: int = 0, bias=None, residual=None, _route=None):
+    """A [M, K] bf16 (ANY number of rows: the drafter's prompt prefill) @ the packed weight, epilogues as linear_rows_streamk: the pieces of
+    drafter_gemm_route("packed"), written into one result (bf16: lantern_linear_rows_packed, row blocks of 128 -- 64 for a gate / up pair -- re-stream
+    the weight tile; fp8: lantern_linear_rows_packed_fmt, or the stream-K kernel block by block).  (`_route`: the pieces, from a caller that has routed already.)"""
     if not isinstance(weight, PackedLinearWeight):
         raise _lib.LanternError("linear_rows_packed: weight must be a PackedLinearWeight (pack_linear_weight)")
     if not A.is_cuda or A.dtype != torch.bfloat16:
@@ -770,24 +816,29 @@ def linear_rows_packed(A, weight: "PackedLinearWeight", epilogue: int = 0, bias=
     M, K = A.shape
     if K != weight.K or (epilogue == EPI_SILU_MUL) != (weight.pair_rows > 0):
         raise _lib.LanternError("linear_rows_packed: the packed weight does not match this call (K, gate / up pairing)")
-    if weight.fmt == "fp8" and M < _lib.get_tuning("gemm_tiled_from"):
-        # 33 - 128 rows have no fp8 kernel of their own: they go through the stream-K kernel in blocks of at most 32
-        if M == 0:
-            return torch.empty((0, weight.n_rows), dtype=torch.bfloat16, device=A.device)
-        return torch.cat([linear_rows_streamk(A[m0:m0 + 32], weight, epilogue, bias=bias, residual=None if residual is None else residual[m0:m0 + 32])
-                          for m0 in range(0, M, 32)], dim=0)
     out = torch.empty((M, weight.n_rows), dtype=torch.bfloat16, device=A.device)
     r = None if residual is None else residual.contiguous()
     b = None if bias is None else bias.contiguous()
-    if weight.fmt == "fp8":
-        check(_lib.lib().lantern_linear_rows_packed_fmt(C.c_void_p(A.data_ptr()), C.c_void_p(weight.data.data_ptr()), C.c_void_p(_ptr(b)), M, K, weight.n_rows,
-                                                        C.c_void_p(out.data_ptr()), weight.n_rows, int(epilogue), C.c_void_p(_ptr(r)), 0 if r is None else r.shape[1],
-                                                        int(weight.pair_rows), weight.code, _stream()), "linear_rows_packed_fmt")
-        return out
-    check(_lib.lib().lantern_linear_rows_packed(C.c_void_p(A.data_ptr()), C.c_void_p(weight.data.data_ptr()), C.c_void_p(_ptr(b)), M, K, weight.n_rows,
-                                                C.c_void_p(out.data_ptr()), weight.n_rows, int(epilogue), C.c_void_p(_ptr(r)), 0 if r is None else r.shape[1],
-                                                int(weight.pair_rows), _stream()), "linear_rows_packed")
+    for kernel, m0, m in _route or drafter_gemm_route("packed", M, _weight_form(weight), True, _tiled_from):
+        if kernel == "linear_rows_streamk":
+            linear_rows_streamk(A[m0:m0 + m], weight, epilogue, bias=b, residual=None if r is None else r[m0:m0 + m], out=out[m0:m0 + m])
+        else:
+            args = (C.c_void_p(A.data_ptr()), C.c_void_p(weight.data.data_ptr()), C.c_void_p(_ptr(b)), M, K, weight.n_rows, C.c_void_p(out.data_ptr()), weight.n_rows,
+                    int(epilogue), C.c_void_p(_ptr(r)), 0 if r is None else r.shape[1], int(weight.pair_rows))
+            if kernel == "linear_rows_packed_fmt":
+                check(_lib.lib().lantern_linear_rows_packed_fmt(*args, weight.code, _stream()), "linear_rows_packed_fmt")
+            else:
+                check(_lib.lib().lantern_linear_rows_packed(*args, _stream()), "linear_rows_packed")
     return out
+
+
+def drafter_linear(A, weight, epilogue: int = 0, bias=None, residual=None, pair_rows: int = 0):
+    """One GEMM of the drafter's decoder layer at any row count, as drafter_gemm_route("layer") says (`pair_rows`: for a row-major gate / up weight)."""
+    M, K = A.shape
+    route = drafter_gemm_route("layer", M, _weight_form(weight), K % 64 == 0, _tiled_from)
+    if len(route) == 1 and route[0][0] == "linear_rows_streamk":
+        return linear_rows_streamk(A, weight, epilogue, bias=bias, residual=residual, pair_rows=pair_rows)
+    return linear_rows_packed(A, weight, epilogue, bias=bias, residual=residual, _route=route)          # (every other piece list is linear_rows_packed's to run)
 
 
 def rmsnorm_rows(x, weight, eps: float):
@@ -952,46 +1003,67 @@ def mask_left_padding(attention_mask, out=None):
     return out
 
 
-def drafter_fc(ids, hidden, embed, weight, bias=None, embed_scale: float = 1.0, packed: Optional["PackedLinearWeight"] = None):
+def _input_route(M: int, H: int, packed):
+    """(a packed weight only counts where H % 64 == 0: K = 2H can be packed at H % 64 == 32, but no input-stage kernel reads those bricks)"""
+    form = _weight_form(packed) if packed is not None and H % 64 == 0 else W_ROWS
+    return drafter_gemm_route("input", M, form, H % 64 == 0, _tiled_from)
+
+
+def drafter_fc(ids, hidden, embed, weight, bias=None, embed_scale: float = 1.0, packed: Optional["PackedLinearWeight"] = None, out=None, _kernel=None):
     """O11 (MFMA): fc(cat(embed[ids] * scale, hidden)) -> bf16 [M,H].  ids [M] i64, hidden [M,H] bf16, embed [vocab,H] bf16,
-    weight [H,2H] bf16 (nn.Linear layout), bias [H] bf16 or None.  Up to 32 rows with H % 64 == 0 (the drafting shape) take the stream-K
-    kernel, on `packed` = pack_linear_weight(weight) when given.  An fp8 `packed` at prefill row counts ("gemm_tiled_from" rows and more, default 129): one
-    launch of the tiled kernel's gather form (lantern_drafter_fc_packed); 33 rows up to that threshold: stream-K blocks of 32."""
+    weight [H,2H] bf16 (nn.Linear layout), bias [H] bf16 or None, `packed` = pack_linear_weight(weight) when the caller has it.  Any number of rows:
+    the kernel drafter_gemm_route("input") names -- up to 32 rows with H % 64 == 0 (the drafting shape) the stream-K kernel, an fp8 `packed` from
+    "gemm_tiled_from" rows one launch of the tiled kernel's gather form --, or, where the route has several pieces, one drafter_fc call per piece.
+    `out`: a contiguous [M, H] bf16 tensor to write (a row block of a larger result); `_kernel`: the piece's kernel, from a caller that has routed."""
     for t, n in ((hidden, "hidden"), (embed, "embed"), (weight, "weight")):
         if not t.is_cuda or t.dtype != torch.bfloat16:
             raise _lib.LanternError(f"drafter_fc: {n} must be a bf16 device tensor")
     ids = _dev(ids, torch.int64, "ids").reshape(-1)
     hidden, embed, weight = hidden.contiguous(), embed.contiguous(), weight.contiguous()
-    M, H = hidden.reshape(-1, hidden.shape[-1]).shape
+    hidden = hidden.reshape(-1, hidden.shape[-1])
+    M, H = hidden.shape
     assert weight.shape == (H, 2 * H) and embed.shape[1] == H and ids.numel() == M
-    out = torch.empty((M, H), dtype=torch.bfloat16, device=hidden.device)
-    b = None if bias is None else bias.contiguous()
-    if packed is not None and packed.fmt == "fp8" and (M > 32 or H % 64):
-        if H % 64:
-            raise _lib.LanternError(f"drafter_fc: an fp8 packed weight needs H % 64 == 0 (H = {H})")
-        if M >= _lib.get_tuning("gemm_tiled_from"):
-            if packed.K != 2 * H or packed.n_rows != H or packed.pair_rows:
-                raise _lib.LanternError("drafter_fc: the packed weight is not this fc's [H, 2H] weight")
-            check(_lib.lib().lantern_drafter_fc_packed(C.c_void_p(ids.data_ptr()), C.c_void_p(hidden.data_ptr()), C.c_void_p(embed.data_ptr()),
-                                                       C.c_void_p(packed.data.data_ptr()), C.c_void_p(_ptr(b)), M, H, embed.shape[0], C.c_float(embed_scale),
-                                                       C.c_void_p(out.data_ptr()), packed.code, _stream()), "drafter_fc_packed")
-            return out
-        # 33 rows up to the tiled kernel's threshold go through the stream-K kernel in blocks of 32 (never onto the bf16 row-major weight unnoticed)
-        return torch.cat([drafter_fc(ids[m0:m0 + 32], hidden.reshape(M, H)[m0:m0 + 32], embed, weight, bias, embed_scale, packed) for m0 in range(0, M, 32)], dim=0)
-    if M <= 32 and H % 64 == 0:
-        if packed is not None and (packed.K != 2 * H or packed.n_rows != H or packed.pair_rows):
-            raise _lib.LanternError("drafter_fc: the packed weight is not this fc's [H, 2H] weight")
+    if packed is not None and packed.fmt == "fp8" and H % 64:
+        raise _lib.LanternError(f"drafter_fc: an fp8 packed weight needs H % 64 == 0 (H = {H})")
+    kernel = _kernel
+    if kernel is None:
+        route = _input_route(M, H, packed)
+        if len(route) > 1:
+            return _fc_pieces(route, ids, hidden, embed, weight, bias, embed_scale, packed, out)
+        kernel = route[0][0]
+    if out is None:
+        out = torch.empty((M, H), dtype=torch.bfloat16, device=hidden.device)
+    assert out.shape == (M, H) and out.dtype == torch.bfloat16 and out.is_contiguous()
+    if kernel in ("drafter_fc_packed", "drafter_fc_streamk") and (packed.K != 2 * H or packed.n_rows != H or packed.pair_rows):
+        raise _lib.LanternError("drafter_fc: the packed weight is not this fc's [H, 2H] weight")
+    L, b = _lib.lib(), None if bias is None else bias.contiguous()
+    args = (C.c_void_p(ids.data_ptr()), C.c_void_p(hidden.data_ptr()), C.c_void_p(embed.data_ptr()))
+    tail = (C.c_void_p(_ptr(b)), M, H, embed.shape[0], C.c_float(embed_scale), C.c_void_p(out.data_ptr()))
+    if kernel == "drafter_fc_packed":
+        check(L.lantern_drafter_fc_packed(*args, C.c_void_p(packed.data.data_ptr()), *tail, packed.code, _stream()), "drafter_fc_packed")
+    elif kernel == "drafter_fc":
+        check(L.lantern_drafter_fc(*args, C.c_void_p(weight.data_ptr()), *tail, _stream()), "drafter_fc")
+    else:
+        pk = packed if kernel == "drafter_fc_streamk" else None
         sk = _sk_workspace(hidden.device)
-        wt = weight if packed is None else packed.data
-        check(_lib.lib().lantern_drafter_fc_streamk(C.c_void_p(ids.data_ptr()), C.c_void_p(hidden.data_ptr()), C.c_void_p(embed.data_ptr()),
-                                                    C.c_void_p(wt.data_ptr()), C.c_void_p(_ptr(b)), M, H, embed.shape[0], C.c_float(embed_scale),
-                                                    C.c_void_p(out.data_ptr()), _packed_code(packed), C.c_void_p(sk.data_ptr()), C.c_size_t(sk.numel()),
-                                                    _stream()), "drafter_fc_streamk")
-        return out
-    check(_lib.lib().lantern_drafter_fc(C.c_void_p(ids.data_ptr()), C.c_void_p(hidden.data_ptr()), C.c_void_p(embed.data_ptr()),
-                                        C.c_void_p(weight.data_ptr()), C.c_void_p(_ptr(b)), M, H, embed.shape[0], C.c_float(embed_scale),
-                                        C.c_void_p(out.data_ptr()), _stream()), "drafter_fc")
+        check(L.lantern_drafter_fc_streamk(*args, C.c_void_p((weight if pk is None else pk.data).data_ptr()), *tail, _packed_code(pk), C.c_void_p(sk.data_ptr()),
+                                           C.c_size_t(sk.numel()), _stream()), "drafter_fc_streamk")
     return out
+
+
+def _fc_pieces(route, ids, hidden, embed, weight, bias, embed_scale, packed, out=None):
+    """Every piece of an input-stage route as one drafter_fc call (one kernel) on its rows, with the weight form the piece names, into one [M, H] result."""
+    if out is None:
+        out = torch.empty(hidden.shape, dtype=torch.bfloat16, device=hidden.device)
+    for kernel, m0, m in route:
+        pk = None if kernel in ("drafter_fc", "drafter_fc_streamk/row-major") else packed
+        drafter_fc(ids[m0:m0 + m], hidden[m0:m0 + m], embed, weight, bias, embed_scale, packed=pk, out=out[m0:m0 + m], _kernel=kernel)
+    return out
+
+
+def drafter_input_stage(ids, hidden, embed, weight, bias=None, embed_scale: float = 1.0, packed: Optional["PackedLinearWeight"] = None):
+    """The drafter's input stage on ids [M] / hidden [M, H] of any row count: drafter_fc with EVERY piece of the route as a drafter_fc call, a single one too."""
+    return _fc_pieces(_input_route(*hidden.shape, packed), ids, hidden, embed, weight, bias, embed_scale, packed)
 
 
 def pack_vq_table(table, cols: int):

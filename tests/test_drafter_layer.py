@@ -491,3 +491,43 @@ def test_layer_prefill_runs_on_the_hip_path_and_matches_the_torch_path(kind, nam
         np.testing.assert_allclose(y1[b].float().cpu().numpy(), r1[b].cpu().numpy(), rtol=4e-2, atol=4e-2)
         for got, want in zip(kv1, rkv1):
             np.testing.assert_allclose(got[b, :, st:].float().cpu().numpy(), want[b, :, st:].cpu().numpy(), rtol=4e-2, atol=4e-2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fmt", ["bf16", "fp8"])
+@pytest.mark.parametrize("kind,name", [("lumina", "hd64_gqa"), ("llamagen", "lg_hd64"), ("llamagen", "lg_hd64_idx1"), ("anole", "an_hd64")])
+def test_one_fused_body_serves_every_layer_kind_and_repeats_its_bits(kind, name, fmt):
+    """DecoderLayer._fast is the only fused body: each layer kind runs a 2 x 40 causal prefill (80 rows: the GEMMs above the stream-K shape, the second
+    row left-padded by 3) and, behind its cache, the drafting shape of 20 rows (2 x 10) under ancestor words -- through torch.cat and through the
+    slab cache, twice each: the same bits every time (no workspace state, no dependence on the cache form)."""
+    from lantern_amd.drafters.decoder_layer import DecoderLayer as DL, LlamaDecoderLayer, precompute_freqs_cis_2d
+    assert LlamaDecoderLayer._fast is DL._fast          # one implementation
+    dev, bf = torch.device("cuda"), torch.bfloat16
+    mk = {"lumina": build, "anole": build_an, "llamagen": build_lg}[kind]
+    T0, T1, starts = 40, 10, [0, 3]
+    outs = []
+    for inplace in (False, True, False, True):
+        layer = mk(name, dev, bf)
+        layer.weight_format, layer.inplace_cache = fmt, inplace
+        H, d = layer.self_attn.hidden_size, layer.self_attn.head_dim
+        gen = torch.Generator(device="cuda").manual_seed(len(name) + T0)
+        x0, x1 = (torch.randn(2, T, H, device=dev, generator=gen).to(bf) for T in (T0, T1))
+        if kind == "llamagen":
+            table = precompute_freqs_cis_2d(16, d, 10000, 20).to(dev)
+            pos0, pos1 = torch.arange(T0, device=dev)[None], torch.arange(T0, T0 + T1, device=dev)[None]
+            kw0, kw1 = dict(freqs_cis=table[pos0[0]]), dict(freqs_cis=table[pos1[0]])
+        else:
+            st = torch.tensor(starts, device=dev)[:, None]
+            pos0, pos1 = (torch.arange(T0, device=dev)[None] - st).clamp(min=0), torch.arange(T0, T0 + T1, device=dev)[None] - st
+            kw0 = kw1 = {}
+        ks = torch.tensor(starts, dtype=torch.int64, device=dev)
+        # a small tree over the T1 new tokens: token i sees itself and every third token in front of it
+        bits = torch.tensor([(1 << i) | sum(1 << j for j in range(0, i, 3)) for i in range(T1)], dtype=torch.int64, device=dev)
+        with torch.no_grad():
+            y0, kv0 = layer(x0, position_ids=pos0, use_cache=True, causal=True, kv_start=ks, **kw0)
+            y1, kv1 = layer(x1, position_ids=pos1, past_key_value=kv0, use_cache=True, tree_bits=bits, tree_keys=T1, kv_start=ks, **kw1)
+        outs.append([t.clone() for t in (y0, y1, kv1[0], kv1[1])])
+    assert all(bool(torch.isfinite(t.float()).all()) for t in outs[0])
+    for other in outs[1:]:
+        for a, b in zip(outs[0], other):
+            assert a.shape == b.shape and torch.equal(a, b)

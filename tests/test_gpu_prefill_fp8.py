@@ -298,3 +298,99 @@ def test_fp8_drafter_prefill_runs_the_input_stage_in_one_call(monkeypatch):
     # scale, brick or row order would miss by a factor of several.
     d = (y8.float() - y16.float())[:, 3:].abs().max().item()
     assert d <= 0.125 * y16.float()[:, 3:].abs().max().item(), d
+
+
+# ----------------------------------------------------------------------------------------------------------------- 7. the route, piece by piece
+def _c_drafter_fc(ids, hid, embed, W, bias, scale):
+    """lantern_drafter_fc itself: the per-tile kernel on the row-major weight"""
+    M, H = hid.shape
+    out = torch.full((M, H), float("nan"), dtype=BF, device=hid.device)
+    rc = _lib.lib().lantern_drafter_fc(_ptr(ids), _ptr(hid), _ptr(embed), _ptr(W), _ptr(bias), M, H, embed.shape[0], C.c_float(scale), _ptr(out), ops._stream())
+    assert rc == 0, _lib.lib().lantern_last_error()
+    return out
+
+
+def _c_drafter_fc_streamk(ids, hid, embed, wt, bias, scale, code):
+    """lantern_drafter_fc_streamk itself on `wt`: the row-major weight (code 0) or a packed weight's bricks (code 1 / 2)"""
+    M, H = hid.shape
+    out = torch.full((M, H), float("nan"), dtype=BF, device=hid.device)
+    ws = ops._sk_workspace(hid.device)
+    rc = _lib.lib().lantern_drafter_fc_streamk(_ptr(ids), _ptr(hid), _ptr(embed), _ptr(wt), _ptr(bias), M, H, embed.shape[0], C.c_float(scale), _ptr(out), code,
+                                               _ptr(ws), C.c_size_t(ws.numel()), ops._stream())
+    assert rc == 0, _lib.lib().lantern_last_error()
+    return out
+
+
+def _fc_inputs(M, H=128, vocab=512):
+    gen = torch.Generator().manual_seed(1000 + M)
+    W = (torch.randn(H, 2 * H, generator=gen) / (2 * H) ** 0.5).to(BF).cuda()
+    embed = torch.randn(vocab, H, generator=gen).to(BF).cuda()
+    bias = (0.1 * torch.randn(H, generator=gen)).to(BF).cuda()
+    ids = torch.randint(0, vocab, (M,), generator=gen).cuda()
+    hid = torch.randn(M, H, generator=gen).to(BF).cuda()
+    return ids, hid, embed, W, bias
+
+
+@pytest.mark.parametrize("M", [20, 40, 150])
+def test_bf16_input_stage_equals_the_kernels_its_route_names(M, monkeypatch):
+    """ops.drafter_input_stage / ops.drafter_fc at any row count = the single-kernel calls of ops.drafter_gemm_route("input"), issued by hand through the C
+    entries, bit for bit: 20 rows stream-K on the packed weight; 40 rows lantern_drafter_fc; 150 rows 128 on lantern_drafter_fc and the 22-row tail on
+    stream-K with the ROW-MAJOR weight (the oddity the route's docstring records)."""
+    ids, hid, embed, W, bias = _fc_inputs(M)
+    p16 = ops.pack_linear_weight(W)
+    scale = 2.0
+    if M == 20:
+        want = _c_drafter_fc_streamk(ids, hid, embed, p16.data, bias, scale, 1)
+    elif M == 40:
+        want = _c_drafter_fc(ids, hid, embed, W, bias, scale)
+    else:
+        want = torch.cat([_c_drafter_fc(ids[:128], hid[:128], embed, W, bias, scale), _c_drafter_fc_streamk(ids[128:], hid[128:], embed, W, bias, scale, 0)])
+    assert ops.drafter_gemm_route("input", 150, ops.W_PACKED, True, _lib.get_tuning("gemm_tiled_from")) == [("drafter_fc", 0, 128), ("drafter_fc_streamk/row-major", 128, 22)]
+    pieces = []
+    real = ops.drafter_fc
+    monkeypatch.setattr(ops, "drafter_fc", lambda ids_, hid_, *a, **k_: (pieces.append((hid_.shape[0], getattr(k_.get("packed"), "fmt", None))), real(ids_, hid_, *a, **k_))[1])
+    got = ops.drafter_input_stage(ids, hid, embed, W, bias, scale, p16)
+    assert pieces == {20: [(20, "bf16")], 40: [(40, None)], 150: [(128, None), (22, None)]}[M]
+    assert got.shape == want.shape and torch.equal(got, want)
+    assert torch.equal(real(ids, hid, embed, W, bias, embed_scale=scale, packed=p16), want)          # ops.drafter_fc takes any row count too
+    assert torch.equal(real(ids, hid, embed, W, bias, embed_scale=scale), want if M != 20 else _c_drafter_fc_streamk(ids, hid, embed, W, bias, scale, 0))
+
+
+@pytest.mark.parametrize("M", [40, 128, 129])
+def test_fp8_input_stage_equals_the_kernels_its_route_names(M):
+    """The same for an fp8 packed weight: below "gemm_tiled_from" (129) stream-K blocks of 32 rows on the packed weight, from there one lantern_drafter_fc_packed."""
+    assert _lib.get_tuning("gemm_tiled_from") == 129
+    ids, hid, embed, W, bias = _fc_inputs(M)
+    p8 = ops.pack_linear_weight(W, fmt="fp8")
+    if M >= 129:
+        want = _c_drafter_fc_packed(ids, hid, embed, p8, bias, 2.0, 2)
+    else:
+        want = torch.cat([_c_drafter_fc_streamk(ids[m:m + 32], hid[m:m + 32], embed, p8.data, bias, 2.0, 2) for m in range(0, M, 32)])
+    for fn in (ops.drafter_input_stage, ops.drafter_fc):
+        got = fn(ids, hid, embed, W, bias, 2.0, p8)
+        assert got.shape == (M, 128) and torch.equal(got, want)
+
+
+@pytest.mark.parametrize("fmt", ["bf16", "fp8"])
+@pytest.mark.parametrize("M", [32, 33, 129])
+def test_layer_gemm_equals_the_kernels_its_route_names(M, fmt):
+    """ops.drafter_linear (the decoder layer's GEMM) at K = 320, N = 40 with the residual epilogue: 32 rows one stream-K call; 33 rows bf16 one
+    lantern_linear_rows_packed, fp8 stream-K blocks of 32 + 1 rows; 129 rows bf16 lantern_linear_rows_packed, fp8 one lantern_linear_rows_packed_fmt."""
+    K, N = 320, 40
+    gen = torch.Generator().manual_seed(5 + M)
+    W = (torch.randn(N, K, generator=gen) / K ** 0.5).to(BF).cuda()
+    pk = ops.pack_linear_weight(W, fmt=fmt)
+    x, b, res, kw = _gemm_inputs(M, K, N, 1, gen)
+    if M <= 32:
+        want = ops.linear_rows_streamk(x, pk, 1, bias=b, residual=res)
+    elif fmt == "bf16":
+        want = torch.full((M, N), float("nan"), dtype=BF, device=x.device)
+        rc = _lib.lib().lantern_linear_rows_packed(_ptr(x), _ptr(pk.data), _ptr(b), M, K, N, _ptr(want), N, 1, _ptr(res), N, 0, ops._stream())
+        assert rc == 0, _lib.lib().lantern_last_error()
+    elif M < 129:
+        want = torch.cat([ops.linear_rows_streamk(x[m:m + 32], pk, 1, bias=b, residual=res[m:m + 32]) for m in range(0, M, 32)])
+    else:
+        want = _c_linear_rows_packed_fmt(x, pk, 1, b, res, 2)
+    got = ops.drafter_linear(x, pk, 1, bias=b, residual=res)
+    assert got.shape == (M, N) and torch.equal(got, want)
+    assert torch.equal(ops.drafter_linear(x, pk, 1, bias=b, residual=res), got)
