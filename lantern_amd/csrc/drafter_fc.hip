@@ -1613,7 +1613,7 @@ extern "C" int lantern_linear_rows_epilogue(const void *A, const void *W, const 
 }
 
 extern "C" int lantern_rmsnorm_rows(const void *x, const void *weight, int M, int H, float eps, void *out, void *stream) {
-    LANTERN_CHECK_ARG(x && weight && out && M >= 0 && H > 0, "rmsnorm_rows: bad arguments");
+    LANTERN_CHECK_ARG(weight && M >= 0 && H > 0 && (M == 0 || (x && out)), "rmsnorm_rows: bad arguments");          // (no rows: an empty tensor's pointer is null)
     if (M == 0) return LANTERN_OK;
     LANTERN_LAUNCH(rmsnorm_rows_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)x, (const uint16_t *)weight, H, eps, (uint16_t *)out);
     LANTERN_CHECK_LAUNCH("rmsnorm_rows");
