@@ -875,6 +875,43 @@ int lantern_tree_attention(const void *q, const void *k_cache, const void *v_cac
                            const int64_t *kv_start, int64_t max_kv_len, const uint64_t *tree_bits, int bits_per_row,
                            float scale, void *workspace, size_t workspace_bytes, void *stream);
 
+/* FP8 KV cache (opt-in, next to the bf16 cache; activations, queries and probabilities stay bf16).
+ * A cache row -- one key or value vector of one (batch row, kv head, position) -- is d + 16 bytes:
+ *   bytes 0 .. d-1      e4m3fn codes of the row's d elements
+ *   bytes d .. d+3      the row's scale as an f32, always a power of two, 2^e
+ *   bytes d+4 .. d+15   written as zero, ignored by readers
+ * so a slab is uint8 [..., S_max, d + 16] (144 bytes per row at d = 128, 80 at d = 64: 0.5625 / 0.625 of the bf16 bytes).  The scale lives
+ * in the row: a row stays a multiple of 16 bytes and is self-contained, and lantern_kv_gather / lantern_update_inference_inputs move codes
+ * and scales together, untouched, with elem_bytes = 1, d = d + 16.
+ * Quantisation of a bf16 row x:  amax = max|x| in f32;  e = the smallest integer with amax <= 448 * 2^e  (m, p = frexp(amax):
+ * e = p - 9 + (m > 0.875)), clamped to [-64, 64], e = 0 for an all-zero row;  code = e4m3fn_rne(x / 2^e), saturating at +-448, never a NaN
+ * code (the division is exact).  Inputs are finite by contract: a non-finite element may give any codes, but only within its own row.
+ * code * 2^e is exactly a bf16 value (3 mantissa bits, exponents far inside bf16's), so a reader that expands a row with
+ * v_cvt_scalef32_pk_bf16_fp8 and the row's scale sees exactly the dequantised bf16 cache.
+ *
+ * lantern_kv8_row_bytes: d + 16 for d in {64, 128}, 0 otherwise.
+ * lantern_kv8_append: quantises T new bf16 rows per (b, h) -- k_new / v_new [dev] with element strides (new_stride_b, new_stride_h,
+ *   new_stride_t), rows of d contiguous elements, multiples of 8 -- into positions pos[b] + t of k_cache / v_cache [dev] (byte strides
+ *   kv_stride_b_bytes, kv_stride_h_bytes, multiples of 16, kv_stride_h_bytes >= S_max * (d + 16)); pos [dev] [B] i64, or NULL: pos0 for
+ *   every row.  One launch for K and V; either pair (k_new, k_cache) or (v_new, v_cache) may be NULL.  A position outside [0, S_max) is
+ *   skipped and never written.  All pointers 16-byte aligned.
+ * lantern_kv8_dequantize: n_rows contiguous fp8 rows -> out_bf16 [n_rows, d] (the read-back for tests and tools).
+ * lantern_tree_attention_kv8: lantern_tree_attention with k_cache / v_cache as fp8 slabs [B,Hkv,S_max,d+16] and kv_stride_b /
+ *   kv_stride_h in BYTES (multiples of 16, kv_stride_h >= max_kv_len * (d + 16)); every other argument, the mask rule, the limits, the
+ *   key-split path and its workspace (lantern_tree_attention_workspace serves both) are the same.  Rows before kv_len[b] must have been
+ *   written by lantern_kv8_append (or be all-zero bytes); rows behind it are never interpreted.  The output equals lantern_tree_attention
+ *   on the dequantised caches bit for bit.  Nothing falls back to bf16: what is not built returns an error with a message. */
+size_t lantern_kv8_row_bytes(int d);
+int lantern_kv8_append(const void *k_new, const void *v_new, void *k_cache, void *v_cache, int B, int Hkv, int T, int d,
+                       int64_t new_stride_b, int64_t new_stride_h, int64_t new_stride_t, int64_t kv_stride_b_bytes,
+                       int64_t kv_stride_h_bytes, const int64_t *pos, int64_t pos0, int64_t S_max, void *stream);
+int lantern_kv8_dequantize(const void *cache, void *out_bf16, int64_t n_rows, int d, void *stream);
+int lantern_tree_attention_kv8(const void *q, const void *k_cache, const void *v_cache, void *out, int B, int Hq, int Hkv, int N,
+                               int d, int64_t q_stride_b, int64_t q_stride_n, int64_t q_stride_h, int64_t kv_stride_b,
+                               int64_t kv_stride_h, int64_t out_stride_b, int64_t out_stride_n, const int64_t *kv_len,
+                               const int64_t *kv_start, int64_t max_kv_len, const uint64_t *tree_bits, int bits_per_row,
+                               float scale, void *workspace, size_t workspace_bytes, void *stream);
+
 /* 8f-1 VQ-distance neighbour table: cdist + per-row ascending order, self excluded.
  * Replaces entrypoints/generate_codebook.py:53-65.  codebook [dev] [K,C] f32 ->
  * table [dev] [K,K-1] u16, K <= 16384 (LlamaGen).  workspace: unused (NULL). */

@@ -163,6 +163,7 @@ def lib():
         _lib.lantern_last_error.restype = C.c_char_p
         _lib.lantern_evaluate_posterior_workspace.restype = C.c_size_t
         _lib.lantern_tree_attention_workspace.restype = C.c_size_t
+        _lib.lantern_kv8_row_bytes.restype = C.c_size_t
         _lib.lantern_evaluate_posterior_nodes_workspace.restype = C.c_size_t
         _lib.lantern_head_expand_workspace.restype = C.c_size_t
         _lib.lantern_linear_rows_streamk_workspace.restype = C.c_size_t
@@ -222,6 +223,7 @@ EXPORTS = [
     "lantern_build_vq_table", "lantern_cfg_mask_topk_window", "lantern_evaluate_posterior_window", "lantern_evaluate_posterior_window_instance",
     "lantern_window_to_dense", "lantern_pack_vq_table", "lantern_update_inference_inputs", "lantern_profile_next_launch", "lantern_drafter_attention_mask", "lantern_linear_rows",
     "lantern_tree_attention_workspace", "lantern_tree_attention",
+    "lantern_kv8_row_bytes", "lantern_kv8_append", "lantern_kv8_dequantize", "lantern_tree_attention_kv8",
     "lantern_tree_node_tables_size", "lantern_tree_node_tables", "lantern_evaluate_posterior_nodes_workspace",
     "lantern_evaluate_posterior_nodes", "lantern_verify_step", "lantern_streams_share_queue", "lantern_gather_candidates_dynamic", "lantern_head_expand_workspace", "lantern_head_expand", "lantern_prepare_step",
     "lantern_linear_rows_epilogue", "lantern_linear_rows_packed", "lantern_linear_rows_splitk", "lantern_linear_rows_streamk_workspace", "lantern_linear_rows_streamk", "lantern_pack_linear_weight_bytes", "lantern_pack_linear_weight", "lantern_pack_linear_weight_fp8_bytes", "lantern_pack_linear_weight_fp8", "lantern_unpack_linear_weight_fp8", "lantern_linear_rows_packed_fmt", "lantern_drafter_fc_packed", "lantern_drafter_fc_streamk", "lantern_head_expand_streamk", "lantern_rmsnorm_rows", "lantern_qk_norm_rope", "lantern_qk_rope_pairs", "lantern_draft_depth", "lantern_head_sample", "lantern_draft_static_inputs", "lantern_mask_left_padding",

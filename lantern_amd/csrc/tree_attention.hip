@@ -22,7 +22,17 @@
 //   * the 4 waves of a workgroup take every 4th key tile; their (m, l, O) are merged once through LDS in wave order (no
 //     float atomics: the result does not depend on timing).  When
 //     B*Hq alone cannot fill 256 CUs the key range is also split over gridDim.y and merged by a second tiny kernel.
+//
+// KV8 = true (lantern_tree_attention_kv8): the caches are the FP8 rows of kv_fp8.hip -- d e4m3 codes, the row's scale 2^e as an f32, 12 ignored bytes.
+// Codes are expanded to bf16 with the row's scale (exact: code * 2^e is a bf16 value) right in front of the places the bf16 kernel uses its loaded
+// values: a lane's K fragment of k-step ks is the 8 code bytes at the same d-columns (one 8-byte load, one scale load per lane and tile), a V chunk of
+// 16 codes becomes the two 16-byte chunks 2ch, 2ch + 1 of the same LDS image.  Same d-column -> MFMA-slot assignment, same image, same everything
+// behind it: the output equals the bf16 kernel's on the dequantised cache bit for bit.  Raw codes wait in registers (half the bf16 instance's K / V
+// staging registers), so the software pipeline is the same: next V loads after the image write, next K loads after the QK products.
+#include <type_traits>
+
 #include "common.h"
+#include "fp8_dev.h"
 
 namespace lantern {
 
@@ -41,7 +51,7 @@ struct TaArgs {
     const uint64_t *bits;
     float *ws;
     int64_t q_sb, q_sn, q_sh;   // element strides of q[b][n][h][:]
-    int64_t kv_sb, kv_sh;       // element strides of the caches (row stride = D)
+    int64_t kv_sb, kv_sh;       // element strides of the caches (row stride = D); KV8: byte strides (row stride = D + 16)
     int64_t o_sb, o_sn;         // element strides of out[b][n][h*D + :]
     int64_t max_kv_len;
     int B, Hq, Hkv, N, bits_per_row, q_groups;
@@ -60,9 +70,10 @@ __device__ __forceinline__ ta_bf16x8_t ta_load8(const uint16_t *p) {
     return __builtin_bit_cast(ta_bf16x8_t, *reinterpret_cast<const uint4 *>(p));
 }
 
-template <int D, int QT>
+template <int D, int QT, bool KV8 = false>
 __global__ __launch_bounds__(TA_THREADS, 2) void tree_attention_kernel(const TaArgs a) {
     constexpr int KS = D / 16, DT = D / 32, CPR = D / 8, VL = (TA_TILE * CPR) / 64, QR = QT * 32;
+    constexpr int RB8 = D + KV8_TAIL, CPR8 = D / 16, VL8 = VL / 2;      // KV8: bytes per row, 16-code chunks per row and per lane and tile
     __shared__ __attribute__((aligned(16))) unsigned char s_v[TA_WAVES][TA_TILE * D * 2];
     __shared__ __attribute__((aligned(16))) float s_o[QR][D + 4];
     __shared__ float s_m[TA_WAVES][QR];
@@ -93,6 +104,8 @@ __global__ __launch_bounds__(TA_THREADS, 2) void tree_attention_kernel(const TaA
     const int tb = t_first + split * per, te = min(t_last, tb + per);
     const uint16_t *kb = a.k + (int64_t)b * a.kv_sb + (int64_t)hk * a.kv_sh;
     const uint16_t *vb = a.v + (int64_t)b * a.kv_sb + (int64_t)hk * a.kv_sh;
+    const unsigned char *kb8 = reinterpret_cast<const unsigned char *>(a.k) + (int64_t)b * a.kv_sb + (int64_t)hk * a.kv_sh;      // KV8 only
+    const unsigned char *vb8 = reinterpret_cast<const unsigned char *>(a.v) + (int64_t)b * a.kv_sb + (int64_t)hk * a.kv_sh;
     const float NEG = -__builtin_huge_valf();
 
     // Q^T fragments and each lane's ancestor word (its query column)
@@ -129,21 +142,40 @@ __global__ __launch_bounds__(TA_THREADS, 2) void tree_attention_kernel(const TaA
     // Software pipeline without extra registers: a tile's V registers are free once written to the LDS image and its K
     // fragments once S^T is computed, so the NEXT tile's V loads are issued right after the image is written and its K
     // loads right after the QK products -- both are in flight during the softmax and the PV products of the current tile.
-    ta_bf16x8_t kf[KS];
-    uint4 vr[VL];
+    typename std::conditional<KV8, uint2, ta_bf16x8_t>::type kf[KS];      // KV8: the 8 code bytes of the same d-columns
+    uint4 vr[KV8 ? VL8 : VL];
+    float ksc = 0.0f, vsc[KV8 ? VL8 : 1];                                 // KV8: the scales of the lane's key row and of its V chunks' rows
     auto load_k = [&](int tile) {
         int64_t krow = ((int64_t)tile << 5) + r;
         krow = krow < len ? krow : len - 1;
-        const uint16_t *kp = kb + krow * D + 8 * hh;
+        if constexpr (KV8) {
+            const unsigned char *kp = kb8 + krow * RB8;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) kf[ks] = ta_load8(kp + 16 * ks);      // 16 contiguous bytes per lane and k-step
+            for (int ks = 0; ks < KS; ++ks) kf[ks] = *reinterpret_cast<const uint2 *>(kp + 8 * hh + 16 * ks);
+            ksc = *reinterpret_cast<const float *>(kp + D);
+        } else {
+            const uint16_t *kp = kb + krow * D + 8 * hh;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) kf[ks] = ta_load8(kp + 16 * ks);      // 16 contiguous bytes per lane and k-step
+        }
     };
     auto load_v = [&](int tile) {   // rows past the end are zeroed: 0 * stale-NaN would poison O
+        if constexpr (KV8) {
 #pragma unroll
-        for (int i = 0; i < VL; ++i) {
-            const int c = lane + 64 * i, row = c / CPR, ch = c % CPR;
-            const int64_t key = ((int64_t)tile << 5) + row;
-            vr[i] = key < len ? *reinterpret_cast<const uint4 *>(vb + key * D + 8 * ch) : make_uint4(0, 0, 0, 0);
+            for (int i = 0; i < VL8; ++i) {
+                const int c = lane + 64 * i, row = c / CPR8, ch = c % CPR8;
+                const int64_t key = ((int64_t)tile << 5) + row;
+                const unsigned char *vp = vb8 + key * RB8;
+                vr[i] = key < len ? *reinterpret_cast<const uint4 *>(vp + 16 * ch) : make_uint4(0, 0, 0, 0);
+                vsc[i] = key < len ? *reinterpret_cast<const float *>(vp + D) : 0.0f;      // (a stale tail may hold a NaN scale)
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < VL; ++i) {
+                const int c = lane + 64 * i, row = c / CPR, ch = c % CPR;
+                const int64_t key = ((int64_t)tile << 5) + row;
+                vr[i] = key < len ? *reinterpret_cast<const uint4 *>(vb + key * D + 8 * ch) : make_uint4(0, 0, 0, 0);
+            }
         }
     };
     int tile = tb + wave;
@@ -154,10 +186,19 @@ __global__ __launch_bounds__(TA_THREADS, 2) void tree_attention_kernel(const TaA
     while (tile < te) {
         const int64_t key0 = (int64_t)tile << 5;
         const int next = tile + TA_WAVES;
+        if constexpr (KV8) {
 #pragma unroll
-        for (int i = 0; i < VL; ++i) {
-            const int c = lane + 64 * i, row = c / CPR, ch = c % CPR;
-            *reinterpret_cast<uint4 *>(vimg + ta_v_off<D>(row, ch)) = vr[i];
+            for (int i = 0; i < VL8; ++i) {
+                const int c = lane + 64 * i, row = c / CPR8, ch = c % CPR8;
+                *reinterpret_cast<ta_bf16x8_t *>(vimg + ta_v_off<D>(row, 2 * ch)) = kv8_expand8(make_uint2(vr[i].x, vr[i].y), vsc[i]);
+                *reinterpret_cast<ta_bf16x8_t *>(vimg + ta_v_off<D>(row, 2 * ch + 1)) = kv8_expand8(make_uint2(vr[i].z, vr[i].w), vsc[i]);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < VL; ++i) {
+                const int c = lane + 64 * i, row = c / CPR, ch = c % CPR;
+                *reinterpret_cast<uint4 *>(vimg + ta_v_off<D>(row, ch)) = vr[i];
+            }
         }
         if (next < te) load_v(next);
 
@@ -167,7 +208,10 @@ __global__ __launch_bounds__(TA_THREADS, 2) void tree_attention_kernel(const TaA
         for (int qt = 0; qt < QT; ++qt) {
             s[qt] = ta_f32x16_t{};
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) s[qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[qt][ks], s[qt], 0, 0, 0);
+            for (int ks = 0; ks < KS; ++ks) {
+                if constexpr (KV8) s[qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kv8_expand8(kf[ks], ksc), qf[qt][ks], s[qt], 0, 0, 0);
+                else s[qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[qt][ks], s[qt], 0, 0, 0);
+            }
         }
         if (next < te) load_k(next);
 
@@ -367,11 +411,11 @@ extern "C" size_t lantern_tree_attention_workspace(int B, int Hq, int N, int d, 
     return (size_t)B * Hq * sh.q_groups * ns * sh.QR * (d + 2) * sizeof(float);
 }
 
-extern "C" int lantern_tree_attention(const void *q, const void *k_cache, const void *v_cache, void *out, int B, int Hq, int Hkv, int N, int d,
-                                      int64_t q_stride_b, int64_t q_stride_n, int64_t q_stride_h, int64_t kv_stride_b, int64_t kv_stride_h,
-                                      int64_t out_stride_b, int64_t out_stride_n, const int64_t *kv_len, const int64_t *kv_start,
-                                      int64_t max_kv_len, const uint64_t *tree_bits, int bits_per_row, float scale, void *workspace,
-                                      size_t workspace_bytes, void *stream) {
+// both entries: `kv8` selects the FP8 row format (byte strides, rows of d + 16 bytes) and the KV8 kernel instances
+static int ta_run(bool kv8, const void *q, const void *k_cache, const void *v_cache, void *out, int B, int Hq, int Hkv, int N, int d, int64_t q_stride_b,
+                  int64_t q_stride_n, int64_t q_stride_h, int64_t kv_stride_b, int64_t kv_stride_h, int64_t out_stride_b, int64_t out_stride_n,
+                  const int64_t *kv_len, const int64_t *kv_start, int64_t max_kv_len, const uint64_t *tree_bits, int bits_per_row, float scale,
+                  void *workspace, size_t workspace_bytes, void *stream) {
     using namespace lantern;
     if (B == 0) return LANTERN_OK;
     LANTERN_CHECK_ARG(q && k_cache && v_cache && out && tree_bits, "tree_attention: null pointer");
@@ -380,11 +424,17 @@ extern "C" int lantern_tree_attention(const void *q, const void *k_cache, const 
     LANTERN_CHECK_ARG(d == 64 || d == 128, "tree_attention: head_dim %d not built (64 or 128)", d);
     LANTERN_CHECK_ARG(max_kv_len >= N, "tree_attention: max_kv_len=%lld < N=%d (the N tree keys must already be appended)",
                       (long long)max_kv_len, N);
-    LANTERN_CHECK_ARG(q_stride_b % 8 == 0 && q_stride_n % 8 == 0 && q_stride_h % 8 == 0 && kv_stride_b % 8 == 0 && kv_stride_h % 8 == 0 &&
+    const int kv_mult = kv8 ? 16 : 8;      // bf16: element strides, 8 elements = 16 bytes; fp8: byte strides
+    LANTERN_CHECK_ARG(q_stride_b % 8 == 0 && q_stride_n % 8 == 0 && q_stride_h % 8 == 0 && kv_stride_b % kv_mult == 0 && kv_stride_h % kv_mult == 0 &&
                           out_stride_b % 8 == 0 && out_stride_n % 8 == 0,
-                      "tree_attention: strides must be multiples of 8 elements (16-byte rows)");
+                      kv8 ? "tree_attention_kv8: q / out strides must be multiples of 8 elements, the caches' byte strides multiples of 16"
+                          : "tree_attention: strides must be multiples of 8 elements (16-byte rows)");
     LANTERN_CHECK_ARG(((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out) % 16 == 0, "tree_attention: pointers must be 16-byte aligned");
-    LANTERN_CHECK_ARG(kv_stride_h >= max_kv_len * d, "tree_attention: kv_stride_h=%lld smaller than max_kv_len*d", (long long)kv_stride_h);
+    if (kv8)
+        LANTERN_CHECK_ARG(kv_stride_h >= max_kv_len * (d + KV8_TAIL), "tree_attention_kv8: kv_stride_h=%lld bytes smaller than max_kv_len*(d+16)",
+                          (long long)kv_stride_h);
+    else
+        LANTERN_CHECK_ARG(kv_stride_h >= max_kv_len * d, "tree_attention: kv_stride_h=%lld smaller than max_kv_len*d", (long long)kv_stride_h);
     const TaShape sh = ta_shape(N, d);
     const int ns = ta_splits(B, Hq, sh.q_groups, max_kv_len);
     if (ns > 1) {
@@ -402,8 +452,13 @@ extern "C" int lantern_tree_attention(const void *q, const void *k_cache, const 
     const int gx = sh.q_groups == 2 ? ((B * Hq + 7) / 8) * 16 : B * Hq;
     const dim3 grid(gx, ns), block(TA_THREADS);
     hipStream_t st = (hipStream_t)stream;
-    if (d == 128) LANTERN_LAUNCH((tree_attention_kernel<128, 1>), grid, block, 0, st, a);
-    else LANTERN_LAUNCH((tree_attention_kernel<64, 1>), grid, block, 0, st, a);
+    if (kv8) {
+        if (d == 128) LANTERN_LAUNCH((tree_attention_kernel<128, 1, true>), grid, block, 0, st, a);
+        else LANTERN_LAUNCH((tree_attention_kernel<64, 1, true>), grid, block, 0, st, a);
+    } else {
+        if (d == 128) LANTERN_LAUNCH((tree_attention_kernel<128, 1>), grid, block, 0, st, a);
+        else LANTERN_LAUNCH((tree_attention_kernel<64, 1>), grid, block, 0, st, a);
+    }
     LANTERN_CHECK_LAUNCH("tree_attention");
     if (ns > 1) {
         const int rows = 256 / (d / 4);
@@ -412,4 +467,22 @@ extern "C" int lantern_tree_attention(const void *q, const void *k_cache, const 
         LANTERN_CHECK_LAUNCH("tree_attention_merge");
     }
     return LANTERN_OK;
+}
+
+extern "C" int lantern_tree_attention(const void *q, const void *k_cache, const void *v_cache, void *out, int B, int Hq, int Hkv, int N, int d,
+                                      int64_t q_stride_b, int64_t q_stride_n, int64_t q_stride_h, int64_t kv_stride_b, int64_t kv_stride_h,
+                                      int64_t out_stride_b, int64_t out_stride_n, const int64_t *kv_len, const int64_t *kv_start,
+                                      int64_t max_kv_len, const uint64_t *tree_bits, int bits_per_row, float scale, void *workspace,
+                                      size_t workspace_bytes, void *stream) {
+    return ta_run(false, q, k_cache, v_cache, out, B, Hq, Hkv, N, d, q_stride_b, q_stride_n, q_stride_h, kv_stride_b, kv_stride_h, out_stride_b,
+                  out_stride_n, kv_len, kv_start, max_kv_len, tree_bits, bits_per_row, scale, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lantern_tree_attention_kv8(const void *q, const void *k_cache, const void *v_cache, void *out, int B, int Hq, int Hkv, int N, int d,
+                                          int64_t q_stride_b, int64_t q_stride_n, int64_t q_stride_h, int64_t kv_stride_b, int64_t kv_stride_h,
+                                          int64_t out_stride_b, int64_t out_stride_n, const int64_t *kv_len, const int64_t *kv_start,
+                                          int64_t max_kv_len, const uint64_t *tree_bits, int bits_per_row, float scale, void *workspace,
+                                          size_t workspace_bytes, void *stream) {
+    return ta_run(true, q, k_cache, v_cache, out, B, Hq, Hkv, N, d, q_stride_b, q_stride_n, q_stride_h, kv_stride_b, kv_stride_h, out_stride_b,
+                  out_stride_n, kv_len, kv_start, max_kv_len, tree_bits, bits_per_row, scale, workspace, workspace_bytes, stream);
 }

@@ -8,21 +8,9 @@
 // i.e. a lane's 16 bytes of half j are its B-fragment elements of MFMA steps 2j and 2j + 1 (8 each), and a wave's 16-byte load is 1 KB contiguous.
 // Behind the bricks: the f32 scales, scale[set * n_pad + n] for the n_pad = 32 * tiles padded rows of each set (1 for the padding rows).
 #include "common.h"
+#include "fp8_dev.h"          // f32_to_e4m3fn
 
 namespace lantern {
-
-// f32 -> e4m3fn, round to nearest even, saturating (|x| >= 464 would round past 448 -> 448; NaN -> 448 with its sign): the arithmetic of torch's
-// float8_e4m3fn conversion on the range a scaled row can reach
-__device__ __forceinline__ uint8_t f32_to_e4m3fn(float x) {
-    const uint32_t u = __float_as_uint(x);
-    const uint8_t sign = (uint8_t)((u >> 24) & 0x80u);
-    const float a = __uint_as_float(u & 0x7fffffffu);
-    if (!(a < 464.0f)) return sign | 0x7e;
-    if (a < 0.015625f) return sign | (uint8_t)__float2int_rn(a * 512.0f);          // subnormal range: multiples of 2^-9 (8 = the smallest normal)
-    uint32_t b = u & 0x7fffffffu;
-    b += 0x7ffffu + ((b >> 20) & 1u);                                              // RNE to 3 mantissa bits (a carry moves into the exponent)
-    return sign | (uint8_t)((((b >> 23) - 120u) << 3) | ((b >> 20) & 7u));
-}
 
 // pass 1: one workgroup per padded row of every set -> its scale
 __global__ __launch_bounds__(256) void fp8_row_scale_kernel(const uint16_t *__restrict__ W, int n_rows, int n_pad, int K, int pair_rows, float *__restrict__ scale) {

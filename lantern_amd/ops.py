@@ -1161,7 +1161,10 @@ def tree_attention(q, k_cache, v_cache, tree_bits, kv_len=None, kv_start=None, m
     q bf16 [B,N,Hq,d] (or any view with a contiguous last dim, e.g. the transposed [B,Hq,N,d] -- pass it as `q.transpose(1,2)`);
     k_cache / v_cache bf16 [B,Hkv,S_max,d] views of the slab (the N tree keys already appended); tree_bits int64 [N] | [B,N]
     (`tree_mask_bits`); kv_len int64 [B] keys per row incl. the tree keys (None: max_kv_len everywhere); kv_start int64 [B]
-    first visible key (left padding; None: 0).  Returns bf16 [B,N,Hq*d]."""
+    first visible key (left padding; None: 0).  Returns bf16 [B,N,Hq*d].
+    uint8 caches [B,Hkv,S_max,d+16] are FP8 slabs (`kv8_append`) and run lantern_tree_attention_kv8; any other dtype raises."""
+    if k_cache.dtype == torch.uint8 or v_cache.dtype == torch.uint8:
+        return _tree_attention_kv8(q, k_cache, v_cache, tree_bits, kv_len, kv_start, max_kv_len, scale, out)
     for t, n in ((q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache")):
         if not t.is_cuda or t.dtype != torch.bfloat16:
             raise _lib.LanternError(f"tree_attention: {n} must be a bf16 device tensor")
@@ -1196,4 +1199,109 @@ def tree_attention(q, k_cache, v_cache, tree_bits, kv_len=None, kv_start=None, m
                                    C.c_int64(max_kv_len), C.c_void_p(bits.data_ptr()), int(bits.dim() == 2),
                                    C.c_float(float(scale) if scale is not None else d ** -0.5), C.c_void_p(_ptr(ws)), C.c_size_t(need),
                                    _stream()), "tree_attention")
+    return out
+
+
+# ------------------------------------------------------------------------ FP8 KV cache (include/lantern_hip.h, "FP8 KV cache")
+
+def kv8_row_bytes(d: int) -> int:
+    """Bytes of one FP8 cache row of head_dim d (d codes + the 16-byte tail that holds the scale): d + 16 for d in {64, 128}, else 0."""
+    return int(_lib.lib().lantern_kv8_row_bytes(int(d)))
+
+
+def _kv8_slab(t, name, what):
+    if not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 4:
+        raise _lib.LanternError(f"{what}: {name} must be a uint8 device tensor [B,Hkv,S_max,d+16]")
+    d = t.shape[3] - 16
+    if kv8_row_bytes(d) != t.shape[3]:
+        raise _lib.LanternError(f"{what}: {name} rows of {t.shape[3]} bytes: need d + 16 with d in (64, 128)")
+    if t.stride(3) != 1 or t.stride(2) != t.shape[3]:
+        raise _lib.LanternError(f"{what}: {name} needs contiguous [S_max, d+16] rows")
+    return d
+
+
+def kv8_append(k_new, v_new, k_cache, v_cache, pos):
+    """Quantise new bf16 K/V rows into FP8 slabs (lantern_kv8_append, one launch).  k_new / v_new bf16 [B,Hkv,T,d] (any view with a contiguous
+    last dim, e.g. the transposed [B,T,Hkv,d]) or None; k_cache / v_cache uint8 [B,Hkv,S_max,d+16] or None with its new rows; pos: an int (the
+    same first position for every batch row) or an int64 device tensor [B].  Rows land at positions pos[b] + t; a position >= S_max is skipped."""
+    pairs = [(n, c, nm) for n, c, nm in ((k_new, k_cache, "k"), (v_new, v_cache, "v")) if n is not None or c is not None]
+    if not pairs:
+        raise _lib.LanternError("kv8_append: nothing to append")
+    n0, c0, _ = pairs[0]
+    for n, c, nm in pairs:
+        if n is None or c is None:
+            raise _lib.LanternError(f"kv8_append: {nm}_new and {nm}_cache come as a pair")
+        if not n.is_cuda or n.dtype != torch.bfloat16 or n.dim() != 4:
+            raise _lib.LanternError(f"kv8_append: {nm}_new must be a bf16 device tensor [B,Hkv,T,d]")
+        d = _kv8_slab(c, f"{nm}_cache", "kv8_append")
+        if tuple(n.shape[:2]) != tuple(c.shape[:2]) or n.shape[3] != d or n.stride(3) != 1:
+            raise _lib.LanternError(f"kv8_append: {nm}_new {tuple(n.shape)} vs {nm}_cache {tuple(c.shape)}")
+        if n.shape != n0.shape or n.stride() != n0.stride() or c.shape != c0.shape or c.stride() != c0.stride():
+            raise _lib.LanternError("kv8_append: K and V must share shapes and strides")
+    B, Hkv, T, d = n0.shape
+    if isinstance(pos, torch.Tensor):
+        pos_t = _dev(pos, torch.int64, "kv8_append: pos").contiguous()
+        if pos_t.numel() != B:
+            raise _lib.LanternError(f"kv8_append: pos must have {B} entries")
+        pos0 = 0
+    else:
+        pos_t, pos0 = None, int(pos)
+    kn, kc = (k_new, k_cache) if k_new is not None else (None, None)
+    vn, vc = (v_new, v_cache) if v_new is not None else (None, None)
+    check(_lib.lib().lantern_kv8_append(C.c_void_p(_ptr(kn)), C.c_void_p(_ptr(vn)), C.c_void_p(_ptr(kc)), C.c_void_p(_ptr(vc)), B, Hkv, T, d,
+                                        C.c_int64(n0.stride(0)), C.c_int64(n0.stride(1)), C.c_int64(n0.stride(2)), C.c_int64(c0.stride(0)),
+                                        C.c_int64(c0.stride(1)), C.c_void_p(_ptr(pos_t)), C.c_int64(pos0), C.c_int64(c0.shape[2]), _stream()),
+          "kv8_append")
+
+
+def kv8_dequantize(cache: torch.Tensor) -> torch.Tensor:
+    """FP8 rows uint8 [..., d+16] (contiguous) -> bf16 [..., d]: codes times the row's scale, exact (lantern_kv8_dequantize)."""
+    if not cache.is_cuda or cache.dtype != torch.uint8 or not cache.is_contiguous():
+        raise _lib.LanternError("kv8_dequantize: a contiguous uint8 device tensor [..., d+16]")
+    d = cache.shape[-1] - 16
+    if kv8_row_bytes(d) != cache.shape[-1]:
+        raise _lib.LanternError(f"kv8_dequantize: rows of {cache.shape[-1]} bytes: need d + 16 with d in (64, 128)")
+    out = torch.empty(cache.shape[:-1] + (d,), dtype=torch.bfloat16, device=cache.device)
+    check(_lib.lib().lantern_kv8_dequantize(C.c_void_p(cache.data_ptr()), C.c_void_p(out.data_ptr()), C.c_int64(out.numel() // d), d, _stream()),
+          "kv8_dequantize")
+    return out
+
+
+def _tree_attention_kv8(q, k_cache, v_cache, tree_bits, kv_len, kv_start, max_kv_len, scale, out):
+    """`tree_attention` on FP8 slabs: the same checks in the slab's terms, byte strides, lantern_tree_attention_kv8."""
+    if not q.is_cuda or q.dtype != torch.bfloat16:
+        raise _lib.LanternError("tree_attention: q must be a bf16 device tensor")
+    dk = _kv8_slab(k_cache, "k_cache", "tree_attention")
+    _kv8_slab(v_cache, "v_cache", "tree_attention")
+    B, N, Hq, d = q.shape
+    Bk, Hkv, S_max, _ = k_cache.shape
+    if (Bk, dk) != (B, d) or v_cache.shape != k_cache.shape or k_cache.stride() != v_cache.stride():
+        raise _lib.LanternError(f"tree_attention: q {tuple(q.shape)} vs fp8 caches {tuple(k_cache.shape)} / {tuple(v_cache.shape)}")
+    if q.stride(3) != 1:
+        raise _lib.LanternError("tree_attention: q needs a contiguous last dim")
+    if max_kv_len is None:
+        max_kv_len = S_max
+    if not N <= max_kv_len <= S_max:
+        raise _lib.LanternError(f"tree_attention: max_kv_len={max_kv_len} outside [N={N}, S_max={S_max}]")
+    bits = _dev(tree_bits, torch.int64, "tree_attention: tree_bits").contiguous()
+    if bits.shape not in ((N,), (B, N)):
+        raise _lib.LanternError(f"tree_attention: tree_bits {tuple(bits.shape)}, expected [{N}] or [{B},{N}]")
+    kl = None if kv_len is None else _dev(kv_len, torch.int64, "tree_attention: kv_len").contiguous()
+    ks = None if kv_start is None else _dev(kv_start, torch.int64, "tree_attention: kv_start").contiguous()
+    for t, n in ((kl, "kv_len"), (ks, "kv_start")):
+        if t is not None and t.numel() != B:
+            raise _lib.LanternError(f"tree_attention: {n} must have {B} entries")
+    if out is None:
+        out = torch.empty((B, N, Hq * d), dtype=torch.bfloat16, device=q.device)
+    assert out.dtype == torch.bfloat16 and out.shape == (B, N, Hq * d) and out.stride(2) == 1
+    L = _lib.lib()
+    need = int(L.lantern_tree_attention_workspace(B, Hq, N, d, C.c_int64(max_kv_len)))
+    ws = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
+    check(L.lantern_tree_attention_kv8(C.c_void_p(q.data_ptr()), C.c_void_p(k_cache.data_ptr()), C.c_void_p(v_cache.data_ptr()),
+                                       C.c_void_p(out.data_ptr()), B, Hq, Hkv, N, d, C.c_int64(q.stride(0)), C.c_int64(q.stride(1)),
+                                       C.c_int64(q.stride(2)), C.c_int64(k_cache.stride(0)), C.c_int64(k_cache.stride(1)),
+                                       C.c_int64(out.stride(0)), C.c_int64(out.stride(1)), C.c_void_p(_ptr(kl)), C.c_void_p(_ptr(ks)),
+                                       C.c_int64(max_kv_len), C.c_void_p(bits.data_ptr()), int(bits.dim() == 2),
+                                       C.c_float(float(scale) if scale is not None else d ** -0.5), C.c_void_p(_ptr(ws)), C.c_size_t(need),
+                                       _stream()), "tree_attention_kv8")
     return out
